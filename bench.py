@@ -3,11 +3,14 @@
 (forward + backward + grad all-reduce + clip + AdamW; 40 000 points/scene, batch 8 per
 GPU, fp32), data-parallel over N MI355X -- BASELINE.json `metric`, workload configs[2].
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `value` = scenes all ranks processed / max-over-ranks
-time of exactly K steps (inputs resident in HBM before the timed region).  `roofline`
+time of exactly K steps (inputs resident in HBM before the timed region), `ms_per_step` = that
+time / K.  A plain run does only this: set-up, W warm-up steps, K timed steps.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs).  `--full` adds the
+parity gate, the roofline entries, the other workloads and the CPU baseline:  `roofline`
 prices the dominant kernel family of the step -- the fp32-MFMA layer kernels of the grouped
 per-seed MLPs (nesie::pw_fwd_kernel / pw_wgrad_kernel) -- from HIP-event timings of every such
 launch; `roofline_step` divides the same FLOPs by the whole step; `parity_gate` is the SURVEY
@@ -778,6 +781,19 @@ def other_workload(device, workload, batch, steps, warmup, gate=True):
     return res
 
 
+def dump_outputs(directory, loss, model, bucket):
+    """What the last timed step hands its caller, as float32 .npy files under ``directory``: the
+    total loss, the flat parameter vector after the update, the flat gradient it was made from and
+    the model's floating-point buffers (normalisation statistics, EMA copies) in state_dict order:
+    about 21 MB for the supervised model, 27 MB for the student/teacher ones, so nothing is sampled."""
+    os.makedirs(directory, exist_ok=True)
+    buffers = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = {'loss': loss.detach(), 'params': bucket.flat_param.detach(), 'grads': bucket.flat,
+              'buffers': torch.cat(buffers) if buffers else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), t.float().cpu().numpy())
+
+
 def spawn_ranks(n, argv, script=None):
     """``python bench.py --gpus N`` without a launcher (WORLD_SIZE unset): start N fresh child
     processes of this script -- one rank per GPU, the torchrun environment contract (RANK,
@@ -861,6 +877,13 @@ def main():
     ap.add_argument('--parity-gate', type=int, default=1,
                     help='0 to skip the CPU-vs-HIP check (index ops, loss dict, gradients) that '
                          'precedes the timing (N = 1 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the parity gate, the '
+                         'un-captured kernel-timed steps behind the roofline entries, the other '
+                         'workloads and the CPU baseline (each still subject to its own switch above)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed -- total loss, '
+                         'flat parameters and gradients, floating-point buffers -- as DIR/<name>.npy')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -882,7 +905,7 @@ def main():
         assert dist.is_initialized() and dist.get_world_size() == args.gpus, \
             f'process group has {dist.get_world_size()} ranks, --gpus {args.gpus}'
     gate = None
-    if args.parity_gate and world == 1:
+    if args.full and args.parity_gate and world == 1:
         gate = parity_gate(device, args.workload)
         if not gate['passed']:
             print(json.dumps({'parity_gate': gate}), flush=True)
@@ -895,75 +918,76 @@ def main():
                                      cfg['optimizer']['lr'], cfg['optimizer']['weight_decay'],
                                      graph=bool(args.graph), workload=args.workload,
                                      resident=args.resident_input)
-    hip = kernels.backend_for(torch.empty(1, device=device))
-    # longest single launch: D-FPS over the 40 000-point scene (latency-bound; in graph mode it
-    # runs on a side stream under the previous step, off the critical path)
-    fps_timer = KernelTimer(hip, 'furthest_point_sampling_wrapper',
-                            lambda b, n, m, *_: n == NUM_POINTS)
-    # largest streaming launches on the critical path: the SA1 MLP tail (B,128,2048,64) through
-    # the fused norm+ReLU+max-pool kernels, and the (B,64,2048,64) layers through norm+ReLU
-    big = args.batch * 128 * 2048 * 64
-    mid = args.batch * 64 * 2048 * 64
-    pool_fwd_timer = KernelTimer(hip, 'bn_relu_maxpool_forward', lambda x, *_: x.numel() == big)
-    pool_bwd_timer = KernelTimer(hip, 'bn_relu_maxpool_backward',
-                                 lambda g, a, x, *_: x.numel() == big)
-    bn_fwd_timer = KernelTimer(hip, 'bn_relu_forward', lambda x, *_: x.numel() == mid)
-    bn_bwd_timer = KernelTimer(hip, 'bn_relu_backward', lambda dy, *_: dy.numel() == mid)
-    # the matrix-core family: every launch of the layer kernel (forward products and, on the
-    # transposed weight view, input gradients) and of the weight-gradient kernel
-    # -> (flop, algorithmic HBM bytes, positions): operands read once, results written once
-    def fwd_flop(x, w, **kw):
-        nb, k, p = x.shape
-        co = w.shape[1]
-        out = nb * co * p * 4 if kw.get('y') is not None else 0
-        tag = ('T' if w.stride(2) != 1 else '') + ('+stats' if kw.get('stat_part') is not None else '') + \
-              ('+pool' if kw.get('pool_group') else '') + ('+rowbias' if kw.get('row_bias') is not None else '') + \
-              ('' if kw.get('y') is not None else '-nostore')
-        return 2.0 * nb * k * co * p, nb * k * p * 4 + out, nb * p, f'[{k}->{co}{tag}, {nb}x{p}]'
+    if args.full:
+        hip = kernels.backend_for(torch.empty(1, device=device))
+        # longest single launch: D-FPS over the 40 000-point scene (latency-bound; in graph mode it
+        # runs on a side stream under the previous step, off the critical path)
+        fps_timer = KernelTimer(hip, 'furthest_point_sampling_wrapper',
+                                lambda b, n, m, *_: n == NUM_POINTS)
+        # largest streaming launches on the critical path: the SA1 MLP tail (B,128,2048,64) through
+        # the fused norm+ReLU+max-pool kernels, and the (B,64,2048,64) layers through norm+ReLU
+        big = args.batch * 128 * 2048 * 64
+        mid = args.batch * 64 * 2048 * 64
+        pool_fwd_timer = KernelTimer(hip, 'bn_relu_maxpool_forward', lambda x, *_: x.numel() == big)
+        pool_bwd_timer = KernelTimer(hip, 'bn_relu_maxpool_backward',
+                                     lambda g, a, x, *_: x.numel() == big)
+        bn_fwd_timer = KernelTimer(hip, 'bn_relu_forward', lambda x, *_: x.numel() == mid)
+        bn_bwd_timer = KernelTimer(hip, 'bn_relu_backward', lambda dy, *_: dy.numel() == mid)
+        # the matrix-core family: every launch of the layer kernel (forward products and, on the
+        # transposed weight view, input gradients) and of the weight-gradient kernel
+        # -> (flop, algorithmic HBM bytes, positions): operands read once, results written once
+        def fwd_flop(x, w, **kw):
+            nb, k, p = x.shape
+            co = w.shape[1]
+            out = nb * co * p * 4 if kw.get('y') is not None else 0
+            tag = ('T' if w.stride(2) != 1 else '') + ('+stats' if kw.get('stat_part') is not None else '') + \
+                  ('+pool' if kw.get('pool_group') else '') + ('+rowbias' if kw.get('row_bias') is not None else '') + \
+                  ('' if kw.get('y') is not None else '-nostore')
+            return 2.0 * nb * k * co * p, nb * k * p * 4 + out, nb * p, f'[{k}->{co}{tag}, {nb}x{p}]'
 
-    def wgrad_flop(dy, x, dw, **kw):
-        nb, co, p = dy.shape
-        return 2.0 * nb * co * x.shape[1] * p, nb * (co + x.shape[1]) * p * 4, nb * p, f'[{co}x{x.shape[1]}, {nb}x{p}]'
+        def wgrad_flop(dy, x, dw, **kw):
+            nb, co, p = dy.shape
+            return 2.0 * nb * co * x.shape[1] * p, nb * (co + x.shape[1]) * p * 4, nb * p, f'[{co}x{x.shape[1]}, {nb}x{p}]'
 
-    def dgrad_flop(dy, w, z, z_coef, da, **kw):   # + the raw output Z of the norm-backward reduction
-        nb, k, p = dy.shape
-        co = w.shape[1]
-        return 2.0 * nb * k * co * p, nb * (k + 2 * co) * p * 4, nb * p, f'[{k}->{co}, {nb}x{p}]'
-    def wgrad_bn_flop(da, z, z_coef, gamma, part, x, dz, dw, *a, **kw):
-        # the weight gradient with the norm backward's apply pass inside: the SAME algorithmic FLOPs
-        # (the per-element transform is not counted); reads dA, Z, X once, writes dZ once
-        nb, co, p = da.shape
-        return 2.0 * nb * co * x.shape[1] * p, nb * (3 * co + x.shape[1]) * p * 4, nb * p, f'[{co}x{x.shape[1]}, {nb}x{p}]'
-    def tail_flop(g, pooled, zstar, argmax, coef, gamma, w, z_prev, coef_prev, ns, *a, **kw):
-        # backward of a pooled tail without its dense tensors (csrc/pool_tail.hip), ALL its launches as
-        # one entry: the layer's input gradient + weight gradient, 2 x 2 nb c k p (what it issues is
-        # 2 nb (k + c) k p built-row product + 2 nb k k p Gram product: the same count at c = 2 k);
-        # reads the operand's raw form twice, writes dA once
-        nb, k, p = z_prev.shape
-        c = w.shape[0]
-        return 4.0 * nb * c * k * p, 3 * nb * k * p * 4, nb * p, f'[{k}->{c}, {nb}x{p}]'
-    # ... and their forms over SA1's rebuilt first activation (Z0 = W0 . X4 is never stored): the same
-    # products, the 64-row operand replaced by the 4 rows of X4 in the byte count; the rebuild's own
-    # 2 * 4 * 64 flop per position are overhead, not counted
-    def fwd_k4_flop(x4, w0, w, in_coef, y, stat_part):
-        nb, _, p = x4.shape
-        co = w.shape[0]
-        return 2.0 * nb * 64 * co * p, nb * (4 + co) * p * 4, nb * p, f'[4=>64->{co}+stats, {nb}x{p}]'
+        def dgrad_flop(dy, w, z, z_coef, da, **kw):   # + the raw output Z of the norm-backward reduction
+            nb, k, p = dy.shape
+            co = w.shape[1]
+            return 2.0 * nb * k * co * p, nb * (k + 2 * co) * p * 4, nb * p, f'[{k}->{co}, {nb}x{p}]'
+        def wgrad_bn_flop(da, z, z_coef, gamma, part, x, dz, dw, *a, **kw):
+            # the weight gradient with the norm backward's apply pass inside: the SAME algorithmic FLOPs
+            # (the per-element transform is not counted); reads dA, Z, X once, writes dZ once
+            nb, co, p = da.shape
+            return 2.0 * nb * co * x.shape[1] * p, nb * (3 * co + x.shape[1]) * p * 4, nb * p, f'[{co}x{x.shape[1]}, {nb}x{p}]'
+        def tail_flop(g, pooled, zstar, argmax, coef, gamma, w, z_prev, coef_prev, ns, *a, **kw):
+            # backward of a pooled tail without its dense tensors (csrc/pool_tail.hip), ALL its launches as
+            # one entry: the layer's input gradient + weight gradient, 2 x 2 nb c k p (what it issues is
+            # 2 nb (k + c) k p built-row product + 2 nb k k p Gram product: the same count at c = 2 k);
+            # reads the operand's raw form twice, writes dA once
+            nb, k, p = z_prev.shape
+            c = w.shape[0]
+            return 4.0 * nb * c * k * p, 3 * nb * k * p * 4, nb * p, f'[{k}->{c}, {nb}x{p}]'
+        # ... and their forms over SA1's rebuilt first activation (Z0 = W0 . X4 is never stored): the same
+        # products, the 64-row operand replaced by the 4 rows of X4 in the byte count; the rebuild's own
+        # 2 * 4 * 64 flop per position are overhead, not counted
+        def fwd_k4_flop(x4, w0, w, in_coef, y, stat_part):
+            nb, _, p = x4.shape
+            co = w.shape[0]
+            return 2.0 * nb * 64 * co * p, nb * (4 + co) * p * 4, nb * p, f'[4=>64->{co}+stats, {nb}x{p}]'
 
-    def dgrad_k4_flop(dy, w, x4, w0, z_coef):
-        nb, k, p = dy.shape
-        return 2.0 * nb * k * 64 * p, nb * (k + 4) * p * 4, nb * p, f'[{k}->64-nostore, {nb}x{p}]'
+        def dgrad_k4_flop(dy, w, x4, w0, z_coef):
+            nb, k, p = dy.shape
+            return 2.0 * nb * k * 64 * p, nb * (k + 4) * p * 4, nb * p, f'[{k}->64-nostore, {nb}x{p}]'
 
-    def wgrad_bn_k4_flop(da, z, z_coef, gamma, part, x4, *a, **kw):
-        nb, co, p = da.shape
-        return 2.0 * nb * co * 64 * p, nb * (3 * co + 4) * p * 4, nb * p, f'[{co}x64<=4, {nb}x{p}]'
-    gemm_timers = (GemmTimer(hip, 'pw_layer_forward', fwd_flop, also=[('pw_layer_forward_k4', fwd_k4_flop)]),
-                   GemmTimer(hip, 'pw_wgrad', wgrad_flop),
-                   GemmTimer(hip, 'pw_dgrad_bn_reduce', dgrad_flop, also=[('pw_dgrad_bn_reduce_k4', dgrad_k4_flop)]),
-                   GemmTimer(hip, 'pw_wgrad_bn_backward', wgrad_bn_flop, also=[('pw_wgrad_bn_backward_k4', wgrad_bn_k4_flop)]),
-                   GemmTimer(hip, 'pool_tail_backward', tail_flop))
-    bn_apply_timer = KernelTimer(hip, 'bn_relu_backward_apply', lambda dy, *_: dy.numel() == mid)
-    timers = (fps_timer, pool_fwd_timer, pool_bwd_timer, bn_fwd_timer, bn_bwd_timer, bn_apply_timer) + gemm_timers
+        def wgrad_bn_k4_flop(da, z, z_coef, gamma, part, x4, *a, **kw):
+            nb, co, p = da.shape
+            return 2.0 * nb * co * 64 * p, nb * (3 * co + 4) * p * 4, nb * p, f'[{co}x64<=4, {nb}x{p}]'
+        gemm_timers = (GemmTimer(hip, 'pw_layer_forward', fwd_flop, also=[('pw_layer_forward_k4', fwd_k4_flop)]),
+                       GemmTimer(hip, 'pw_wgrad', wgrad_flop),
+                       GemmTimer(hip, 'pw_dgrad_bn_reduce', dgrad_flop, also=[('pw_dgrad_bn_reduce_k4', dgrad_k4_flop)]),
+                       GemmTimer(hip, 'pw_wgrad_bn_backward', wgrad_bn_flop, also=[('pw_wgrad_bn_backward_k4', wgrad_bn_k4_flop)]),
+                       GemmTimer(hip, 'pool_tail_backward', tail_flop))
+        bn_apply_timer = KernelTimer(hip, 'bn_relu_backward_apply', lambda dy, *_: dy.numel() == mid)
+        timers = (fps_timer, pool_fwd_timer, pool_bwd_timer, bn_fwd_timer, bn_bwd_timer, bn_apply_timer) + gemm_timers
 
     def sync():
         if world > 1:
@@ -983,23 +1007,26 @@ def main():
             trace.append(loss.detach().clone())
     sync()
     elapsed = time.perf_counter() - t0
-    # Kernel-level timing for the roofline entry: HIP events cannot bracket a kernel inside
-    # a replayed graph, so the same K steps are run once more un-captured with the events
-    # on the launch stream (identical kernels, identical inputs).
-    for t in timers:
-        t.enabled = True
-    eager = getattr(step, 'eager', step)
-    eager_steps = min(args.steps, 5)
-    # (nothing runs beside these launches: they are timed with grids sized for the whole chip, not for
-    # the CUs the replayed step's forward leaves to the sampling kernels)
-    fwd_budget = getattr(step, 'forward_cu_budget', None) or {'cus': 256}
-    budget_in_step, fwd_budget['cus'] = fwd_budget['cus'], 256
-    for _ in range(eager_steps):
-        eager()
-    torch.cuda.synchronize()
-    fwd_budget['cus'] = budget_in_step
-    for t in timers:
-        t.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model, bucket)
+    if args.full:
+        # Kernel-level timing for the roofline entry: HIP events cannot bracket a kernel inside
+        # a replayed graph, so the same K steps are run once more un-captured with the events
+        # on the launch stream (identical kernels, identical inputs).
+        for t in timers:
+            t.enabled = True
+        eager = getattr(step, 'eager', step)
+        eager_steps = min(args.steps, 5)
+        # (nothing runs beside these launches: they are timed with grids sized for the whole chip, not for
+        # the CUs the replayed step's forward leaves to the sampling kernels)
+        fwd_budget = getattr(step, 'forward_cu_budget', None) or {'cus': 256}
+        budget_in_step, fwd_budget['cus'] = fwd_budget['cus'], 256
+        for _ in range(eager_steps):
+            eager()
+        torch.cuda.synchronize()
+        fwd_budget['cus'] = budget_in_step
+        for t in timers:
+            t.enabled = False
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1008,11 +1035,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * args.batch * args.steps / elapsed
-        # FPS 40000->2048: algorithmic HBM bytes per launch = read xyz + temp once, write
-        # temp + idx (DESIGN.md "FPS"): B * (N*12 + N*4 + N*4 + M*4)
-        fps_ms = fps_timer.mean_ms()
-        alg_bytes = args.batch * (NUM_POINTS * 20 + 2048 * 4)
-        achieved = alg_bytes / (fps_ms * 1e-3) / 1e9 if fps_ms else None
         out = {
             'metric': 'ScanNet scenes/sec (fwd+bwd, 40k pts, bs=8)',
             'value': value, 'unit': 'scenes/s', 'n_gpus': world, 'steps': args.steps,
@@ -1046,164 +1068,170 @@ def main():
                                          'during the backbone backward graph, backbone gradients after it',
                        'resident_input_scenes': args.resident_input},
         }
-        # HBM-streaming kernels, priced on their largest launches (537 MB / 268 MB tensors at
-        # B = 8, beyond the 256 MB Infinity Cache).  Algorithmic bytes:
-        #   SA tail backward = gather sums (pooled-size) + read x + write dx      = 2 passes
-        #   SA tail forward  = stats read + pool read                             = 2 passes
-        #   norm+ReLU fwd    = stats read + apply read/write                      = 3 passes
-        #   norm+ReLU bwd    = reduce (dy, y) + apply (dy, x -> dx)               = 5 passes
-        def _stream(name, ms, passes, tensor_bytes, extra=0):
-            if not ms:
-                return None
-            nbytes = passes * tensor_bytes + extra
-            a = nbytes / (ms * 1e-3) / 1e9
-            return {'kernel': name, 'bound': 'hbm', 'achieved': a, 'peak': HBM_PEAK_GBS,
-                    'unit': 'GB/s', 'frac': a / HBM_PEAK_GBS, 'traffic': None,
-                    'avg_launch_ms': ms, 'algorithmic_bytes_per_launch': nbytes}
-        pooled_bytes = args.batch * 128 * 2048 * 4
-        # ---- the dominant family: the grouped per-seed MLP GEMMs on the fp32 matrix cores.
-        # achieved = algorithmic FLOPs (2 * batches * K * Cout * positions per launch) / HIP-event
-        # time, summed over every launch of the family in the un-captured steps.
-        n_l, ms_l, fl_l, by_l = (a + b for a, b in zip(gemm_timers[0].totals(), gemm_timers[2].totals()))
-        n_w, ms_w, fl_w, by_w = gemm_timers[1].totals()
-        # weight-gradient launches that also carry the BatchNorm + ReLU backward's apply pass (dZ formed
-        # on the operand load from (dA, Z) and written once): 4 tensor passes per launch instead of 2,
-        # HBM co-bound -- priced on their own below, and shown inside the family as well
-        n_wf, ms_wf, fl_wf, by_wf = gemm_timers[3].totals()
-        # the pooled tail's backward (built-row input gradient + Gram / sparse weight gradient + its small
-        # launches, timed as ONE entry; of its 3 operand passes the 2 of the layer-kernel launch are in the
-        # PMC family rows)
-        n_t, ms_t, fl_t, by_t = gemm_timers[4].totals()
-        # ... and the same kernels on the 1-D per-seed / per-proposal chains (vote module, prediction
-        # trunk, feature propagation, score heads): 8 x 256 .. 1024 positions, launch-bound
-        sn, sms, sfl, sby = (sum(v) for v in zip(*(t.totals(big=False) for t in gemm_timers)))
-        if n_l + n_w:
-            per_step = lambda v: v / eager_steps  # noqa: E731
-            # THE entry: every launch of the family -- large plain launches, the weight-gradient launches
-            # that carry the norm backward's streaming half, and the small launch-bound 1-D-chain launches
-            fl_all, ms_all = fl_l + fl_w + fl_wf + fl_t + sfl, ms_l + ms_w + ms_wf + ms_t + sms
-            n_all = n_l + n_w + n_wf + n_t + sn
-            tf_all = fl_all / (ms_all * 1e-3) / 1e12
-            tf = (fl_l + fl_w) / ((ms_l + ms_w) * 1e-3) / 1e12
-            binding = binding_roofline(gemm_timers, eager_steps, MFMA_F32_PEAK_TFLOPS, HBM_PEAK_GBS)
-            # HBM bytes of the family as rocprofv3 counted them (separate --pmc FETCH_SIZE / WRITE_SIZE
-            # passes of this command, gfx950 fetch correction applied): produced by tools/make_profiles.py
-            # together with the sha256 of the library that ran; LOADED here, never measured inside this
-            # run, and dropped (null) when the library loaded now is not the one that was profiled
-            traffic, traffic_note = None, None
-            lib_sha = _lib.library_sha256()
-            # a set is for one workload: tools/make_profiles.py records the extra bench arguments it ran with
-            want = {'pretrain': '', 'semi': '--workload semi', 'saqe': '--workload saqe'}[args.workload]
-            cands = []
-            for f in sorted(os.listdir(os.path.join(ROOT, 'profiles'))):
-                if f.endswith('_pmc_hbm_traffic.json'):
-                    if json.load(open(os.path.join(ROOT, 'profiles', f))).get('bench_args', '') == want:
-                        cands.append(f)
-            if args.batch != 8:
-                traffic_note = 'PMC traffic was collected at B = 8 only'
-            elif not cands:
-                traffic_note = f'no profiles/*_pmc_hbm_traffic.json for the {args.workload} workload'
-            else:
-                t = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
-                if t.get('lib_sha256') != lib_sha:
-                    traffic_note = (f'profiles/{cands[-1]} was collected with another build of libnesie_hip.so '
-                                    f'(sha256 {str(t.get("lib_sha256"))[:12]}.. vs loaded {lib_sha[:12]}..): not quoted')
+        if args.full:
+            # FPS 40000->2048: algorithmic HBM bytes per launch = read xyz + temp once, write
+            # temp + idx (DESIGN.md "FPS"): B * (N*12 + N*4 + N*4 + M*4)
+            fps_ms = fps_timer.mean_ms()
+            alg_bytes = args.batch * (NUM_POINTS * 20 + 2048 * 4)
+            achieved = alg_bytes / (fps_ms * 1e-3) / 1e9 if fps_ms else None
+            # HBM-streaming kernels, priced on their largest launches (537 MB / 268 MB tensors at
+            # B = 8, beyond the 256 MB Infinity Cache).  Algorithmic bytes:
+            #   SA tail backward = gather sums (pooled-size) + read x + write dx      = 2 passes
+            #   SA tail forward  = stats read + pool read                             = 2 passes
+            #   norm+ReLU fwd    = stats read + apply read/write                      = 3 passes
+            #   norm+ReLU bwd    = reduce (dy, y) + apply (dy, x -> dx)               = 5 passes
+            def _stream(name, ms, passes, tensor_bytes, extra=0):
+                if not ms:
+                    return None
+                nbytes = passes * tensor_bytes + extra
+                a = nbytes / (ms * 1e-3) / 1e9
+                return {'kernel': name, 'bound': 'hbm', 'achieved': a, 'peak': HBM_PEAK_GBS,
+                        'unit': 'GB/s', 'frac': a / HBM_PEAK_GBS, 'traffic': None,
+                        'avg_launch_ms': ms, 'algorithmic_bytes_per_launch': nbytes}
+            pooled_bytes = args.batch * 128 * 2048 * 4
+            # ---- the dominant family: the grouped per-seed MLP GEMMs on the fp32 matrix cores.
+            # achieved = algorithmic FLOPs (2 * batches * K * Cout * positions per launch) / HIP-event
+            # time, summed over every launch of the family in the un-captured steps.
+            n_l, ms_l, fl_l, by_l = (a + b for a, b in zip(gemm_timers[0].totals(), gemm_timers[2].totals()))
+            n_w, ms_w, fl_w, by_w = gemm_timers[1].totals()
+            # weight-gradient launches that also carry the BatchNorm + ReLU backward's apply pass (dZ formed
+            # on the operand load from (dA, Z) and written once): 4 tensor passes per launch instead of 2,
+            # HBM co-bound -- priced on their own below, and shown inside the family as well
+            n_wf, ms_wf, fl_wf, by_wf = gemm_timers[3].totals()
+            # the pooled tail's backward (built-row input gradient + Gram / sparse weight gradient + its small
+            # launches, timed as ONE entry; of its 3 operand passes the 2 of the layer-kernel launch are in the
+            # PMC family rows)
+            n_t, ms_t, fl_t, by_t = gemm_timers[4].totals()
+            # ... and the same kernels on the 1-D per-seed / per-proposal chains (vote module, prediction
+            # trunk, feature propagation, score heads): 8 x 256 .. 1024 positions, launch-bound
+            sn, sms, sfl, sby = (sum(v) for v in zip(*(t.totals(big=False) for t in gemm_timers)))
+            if n_l + n_w:
+                per_step = lambda v: v / eager_steps  # noqa: E731
+                # THE entry: every launch of the family -- large plain launches, the weight-gradient launches
+                # that carry the norm backward's streaming half, and the small launch-bound 1-D-chain launches
+                fl_all, ms_all = fl_l + fl_w + fl_wf + fl_t + sfl, ms_l + ms_w + ms_wf + ms_t + sms
+                n_all = n_l + n_w + n_wf + n_t + sn
+                tf_all = fl_all / (ms_all * 1e-3) / 1e12
+                tf = (fl_l + fl_w) / ((ms_l + ms_w) * 1e-3) / 1e12
+                binding = binding_roofline(gemm_timers, eager_steps, MFMA_F32_PEAK_TFLOPS, HBM_PEAK_GBS)
+                # HBM bytes of the family as rocprofv3 counted them (separate --pmc FETCH_SIZE / WRITE_SIZE
+                # passes of this command, gfx950 fetch correction applied): produced by tools/make_profiles.py
+                # together with the sha256 of the library that ran; LOADED here, never measured inside this
+                # run, and dropped (null) when the library loaded now is not the one that was profiled
+                traffic, traffic_note = None, None
+                lib_sha = _lib.library_sha256()
+                # a set is for one workload: tools/make_profiles.py records the extra bench arguments it ran with
+                want = {'pretrain': '', 'semi': '--workload semi', 'saqe': '--workload saqe'}[args.workload]
+                cands = []
+                for f in sorted(os.listdir(os.path.join(ROOT, 'profiles'))):
+                    if f.endswith('_pmc_hbm_traffic.json'):
+                        if json.load(open(os.path.join(ROOT, 'profiles', f))).get('bench_args', '') == want:
+                            cands.append(f)
+                if args.batch != 8:
+                    traffic_note = 'PMC traffic was collected at B = 8 only'
+                elif not cands:
+                    traffic_note = f'no profiles/*_pmc_hbm_traffic.json for the {args.workload} workload'
                 else:
-                    traffic = {'fetch_corrected_plus_write_bytes_per_step': t['family_bytes_per_step'],
-                               'over_algorithmic': t['family_bytes_per_step'] / per_step(by_l + by_w + by_wf + by_t * 2 / 3),   # (PMC rows include the fused weight-gradient launches and the pooled tail's layer-kernel launch)
-                               # the family's largest launch by bytes, counted / algorithmic
-                               'largest_launch_over_algorithmic': (
-                                   (t['largest_launch']['fetch_corrected_bytes'] + t['largest_launch']['write_bytes'])
-                                   / max(b_ for tm in (gemm_timers[0], gemm_timers[2]) for (_, b_, *_r) in tm.work)),
-                               'worst_launch': t.get('worst_launch'),
-                               'source': 'profiles/' + cands[-1], 'lib_sha256': lib_sha, 'measured_in_run': False}
-            out['roofline'] = {
-                'kernel': 'nesie::pw_fwd_kernel (forward products + input gradients, with the operand '
-                          'normalisation / statistics / pooling / norm-backward reduction epilogues) + '
-                          'nesie::pw_wgrad_kernel (plain and with the norm backward on its operand load): EVERY '
-                          'launch of the step -- the grouped per-seed MLPs of the SA stacks and the MiniPointNets '
-                          'and the 1-D per-seed / per-proposal chains -- fp32 MFMA (v_mfma_f32_16x16x4_f32)',
-                'bound': 'mfma', 'achieved': tf_all, 'peak': MFMA_F32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': tf_all / MFMA_F32_PEAK_TFLOPS,
-                # the same launches, each priced against the roofline that binds IT (HBM or MFMA)
-                'frac_binding': binding['frac_binding'], 'binding': binding,
-                'traffic': traffic, 'traffic_note': traffic_note,
-                'algorithmic_bytes_per_step': per_step(by_l + by_w + by_wf + by_t),   # launches over >= 32768 positions
-                'algorithmic_hbm_gbs': (by_l + by_w + by_wf + by_t) / ((ms_l + ms_w + ms_wf + ms_t) * 1e-3) / 1e9,
-                'pooled_tail_backward': ({'entries_per_step': per_step(n_t), 'ms_per_step': per_step(ms_t),
-                                          'tflops': fl_t / (ms_t * 1e-3) / 1e12} if ms_t else None),
-                'launches_per_step': per_step(n_all),
-                'family_ms_per_step': per_step(ms_all),
-                'grids': ('timed alone, persistent grids sized for all 256 CUs; inside the replayed step the FORWARD '
-                          f'launches are sized for {budget_in_step} CUs (the next batch\'s sampling kernels hold one '
-                          'CU per XCD meanwhile)' + (f', {fwd_budget.get("late")} from the detection head on' if fwd_budget.get('late') else '')
-                          if budget_in_step != 256 else 'sized for all 256 CUs'),
-                'avg_launch_ms': ms_all / n_all,
-                'algorithmic_flops_per_launch': fl_all / n_all,
-                # sub-entry: the launches over >= 32768 positions WITHOUT the fused norm-backward ones
-                # (what rounds 1-3 quoted as `frac`)
-                'large_plain_launch_subset': {
-                    'launches_per_step': per_step(n_l + n_w), 'ms_per_step': per_step(ms_l + ms_w),
-                    'tflops': tf, 'frac': tf / MFMA_F32_PEAK_TFLOPS,
-                    'layer_kernel': {'launches_per_step': per_step(n_l), 'ms_per_step': per_step(ms_l),
-                                     'tflops': fl_l / (ms_l * 1e-3) / 1e12 if ms_l else None},
-                    'wgrad_kernel': {'launches_per_step': per_step(n_w), 'ms_per_step': per_step(ms_w),
-                                     'tflops': fl_w / (ms_w * 1e-3) / 1e12 if ms_w else None}},
-                # ... and with the fused weight-gradient + norm-backward launches counted as GEMMs
-                # (their streaming half adds time but no FLOPs)
-                'large_launches_with_fused_norm_backward': {
-                    'launches_per_step': per_step(n_l + n_w + n_wf),
-                    'ms_per_step': per_step(ms_l + ms_w + ms_wf),
-                    'tflops': (fl_l + fl_w + fl_wf) / ((ms_l + ms_w + ms_wf) * 1e-3) / 1e12,
-                    'frac': (fl_l + fl_w + fl_wf) / ((ms_l + ms_w + ms_wf) * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS}}
-            if n_wf:
-                gbs = by_wf / (ms_wf * 1e-3) / 1e9
-                out['roofline_fused_norm_backward'] = {
-                    'kernel': 'nesie::pw_wgrad_kernel<..., BNB> (nesie_pw_wgrad_bn_backward): weight gradient '
-                              'with the BatchNorm + ReLU backward apply pass on its operand load; reads dA, Z, X, '
-                              'writes dZ (replaces bn_bwd_apply_kernel + pw_wgrad_kernel: 5 tensor passes -> 4)',
-                    'bound': 'hbm', 'achieved': gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': gbs / HBM_PEAK_GBS, 'traffic': None,
-                    'launches_per_step': per_step(n_wf), 'ms_per_step': per_step(ms_wf),
-                    'avg_launch_ms': ms_wf / n_wf, 'algorithmic_bytes_per_launch': by_wf / n_wf,
-                    'tflops': fl_wf / (ms_wf * 1e-3) / 1e12}
-            if sn:
-                out['roofline_small_layers'] = {
-                    'kernel': 'the same kernels on the 1-D chains (fused_mlp.Stack1dFn): P = 256 .. 1024 '
-                              'positions per scene, one or two tiles per workgroup',
-                    'bound': 'latency', 'launches_per_step': per_step(sn), 'ms_per_step': per_step(sms),
-                    'avg_launch_us': 1e3 * sms / sn, 'tflops': sfl / (sms * 1e-3) / 1e12}
-            # the same FLOPs against the whole step (everything that is not a GEMM counts as lost)
-            step_tf = per_step(fl_l + fl_w + fl_wf + sfl) / (ms_per_step * 1e-3) / 1e12
-            out['roofline_step'] = {'bound': 'mfma', 'achieved': step_tf, 'peak': MFMA_F32_PEAK_TFLOPS,
-                                    'unit': 'TFLOP/s', 'frac': step_tf / MFMA_F32_PEAK_TFLOPS,
-                                    'native_gemm_flop_per_step': per_step(fl_l + fl_w + fl_wf + sfl)}
-        else:
-            out['roofline'] = None
-        out['roofline_streaming'] = [e for e in (
-            _stream('nesie::bn_pool_bwd_reduce_kernel + bn_pool_bwd_apply_kernel<16> (SA1 MLP tail, '
-                    'x (B,128,2048,64))', pool_bwd_timer.mean_ms(), 2, big * 4,
-                    extra=3 * pooled_bytes + pooled_bytes // 4),
-            _stream('nesie::bn_bwd_reduce_kernel + bn_bwd_apply_kernel<relu> (B,64,2048,64)',
-                    bn_bwd_timer.mean_ms(), 5, mid * 4),
-            _stream('nesie::bn_bwd_apply_kernel<relu> from the input-gradient kernel\'s partials '
-                    '(B,64,2048,64): read da, z; write dz', bn_apply_timer.mean_ms(), 3, mid * 4)) if e]
-        rounds = 2047
-        out['roofline_latency_bound'] = {
-            'kernel': 'nesie::fps_pruned_kernel<16> (D-FPS 40000->2048: 2047 DEPENDENT rounds, one '
-                      '1024-thread workgroup per scene; longest single launch, overlapped with the '
-                      'previous step on a side stream in graph mode)',
-            'bound': 'latency', 'achieved': fps_ms * 1e3 / rounds if fps_ms else None,
-            'unit': 'us/round', 'rounds': rounds, 'avg_launch_ms': fps_ms,
-            # what a round re-reads: one 20-byte record per bucket test (625 buckets) + the ~12 active
-            # buckets of 64 points x 16 B from L2 + their running minima from LDS
-            'on_chip_bytes_per_round': 625 * 20 + 12 * 64 * (16 + 4),
-            'compulsory_hbm_bytes_per_launch': alg_bytes, 'peak': None, 'frac': None, 'traffic': None}
+                    t = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
+                    if t.get('lib_sha256') != lib_sha:
+                        traffic_note = (f'profiles/{cands[-1]} was collected with another build of libnesie_hip.so '
+                                        f'(sha256 {str(t.get("lib_sha256"))[:12]}.. vs loaded {lib_sha[:12]}..): not quoted')
+                    else:
+                        traffic = {'fetch_corrected_plus_write_bytes_per_step': t['family_bytes_per_step'],
+                                   'over_algorithmic': t['family_bytes_per_step'] / per_step(by_l + by_w + by_wf + by_t * 2 / 3),   # (PMC rows include the fused weight-gradient launches and the pooled tail's layer-kernel launch)
+                                   # the family's largest launch by bytes, counted / algorithmic
+                                   'largest_launch_over_algorithmic': (
+                                       (t['largest_launch']['fetch_corrected_bytes'] + t['largest_launch']['write_bytes'])
+                                       / max(b_ for tm in (gemm_timers[0], gemm_timers[2]) for (_, b_, *_r) in tm.work)),
+                                   'worst_launch': t.get('worst_launch'),
+                                   'source': 'profiles/' + cands[-1], 'lib_sha256': lib_sha, 'measured_in_run': False}
+                out['roofline'] = {
+                    'kernel': 'nesie::pw_fwd_kernel (forward products + input gradients, with the operand '
+                              'normalisation / statistics / pooling / norm-backward reduction epilogues) + '
+                              'nesie::pw_wgrad_kernel (plain and with the norm backward on its operand load): EVERY '
+                              'launch of the step -- the grouped per-seed MLPs of the SA stacks and the MiniPointNets '
+                              'and the 1-D per-seed / per-proposal chains -- fp32 MFMA (v_mfma_f32_16x16x4_f32)',
+                    'bound': 'mfma', 'achieved': tf_all, 'peak': MFMA_F32_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': tf_all / MFMA_F32_PEAK_TFLOPS,
+                    # the same launches, each priced against the roofline that binds IT (HBM or MFMA)
+                    'frac_binding': binding['frac_binding'], 'binding': binding,
+                    'traffic': traffic, 'traffic_note': traffic_note,
+                    'algorithmic_bytes_per_step': per_step(by_l + by_w + by_wf + by_t),   # launches over >= 32768 positions
+                    'algorithmic_hbm_gbs': (by_l + by_w + by_wf + by_t) / ((ms_l + ms_w + ms_wf + ms_t) * 1e-3) / 1e9,
+                    'pooled_tail_backward': ({'entries_per_step': per_step(n_t), 'ms_per_step': per_step(ms_t),
+                                              'tflops': fl_t / (ms_t * 1e-3) / 1e12} if ms_t else None),
+                    'launches_per_step': per_step(n_all),
+                    'family_ms_per_step': per_step(ms_all),
+                    'grids': ('timed alone, persistent grids sized for all 256 CUs; inside the replayed step the FORWARD '
+                              f'launches are sized for {budget_in_step} CUs (the next batch\'s sampling kernels hold one '
+                              'CU per XCD meanwhile)' + (f', {fwd_budget.get("late")} from the detection head on' if fwd_budget.get('late') else '')
+                              if budget_in_step != 256 else 'sized for all 256 CUs'),
+                    'avg_launch_ms': ms_all / n_all,
+                    'algorithmic_flops_per_launch': fl_all / n_all,
+                    # sub-entry: the launches over >= 32768 positions WITHOUT the fused norm-backward ones
+                    # (what rounds 1-3 quoted as `frac`)
+                    'large_plain_launch_subset': {
+                        'launches_per_step': per_step(n_l + n_w), 'ms_per_step': per_step(ms_l + ms_w),
+                        'tflops': tf, 'frac': tf / MFMA_F32_PEAK_TFLOPS,
+                        'layer_kernel': {'launches_per_step': per_step(n_l), 'ms_per_step': per_step(ms_l),
+                                         'tflops': fl_l / (ms_l * 1e-3) / 1e12 if ms_l else None},
+                        'wgrad_kernel': {'launches_per_step': per_step(n_w), 'ms_per_step': per_step(ms_w),
+                                         'tflops': fl_w / (ms_w * 1e-3) / 1e12 if ms_w else None}},
+                    # ... and with the fused weight-gradient + norm-backward launches counted as GEMMs
+                    # (their streaming half adds time but no FLOPs)
+                    'large_launches_with_fused_norm_backward': {
+                        'launches_per_step': per_step(n_l + n_w + n_wf),
+                        'ms_per_step': per_step(ms_l + ms_w + ms_wf),
+                        'tflops': (fl_l + fl_w + fl_wf) / ((ms_l + ms_w + ms_wf) * 1e-3) / 1e12,
+                        'frac': (fl_l + fl_w + fl_wf) / ((ms_l + ms_w + ms_wf) * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS}}
+                if n_wf:
+                    gbs = by_wf / (ms_wf * 1e-3) / 1e9
+                    out['roofline_fused_norm_backward'] = {
+                        'kernel': 'nesie::pw_wgrad_kernel<..., BNB> (nesie_pw_wgrad_bn_backward): weight gradient '
+                                  'with the BatchNorm + ReLU backward apply pass on its operand load; reads dA, Z, X, '
+                                  'writes dZ (replaces bn_bwd_apply_kernel + pw_wgrad_kernel: 5 tensor passes -> 4)',
+                        'bound': 'hbm', 'achieved': gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': gbs / HBM_PEAK_GBS, 'traffic': None,
+                        'launches_per_step': per_step(n_wf), 'ms_per_step': per_step(ms_wf),
+                        'avg_launch_ms': ms_wf / n_wf, 'algorithmic_bytes_per_launch': by_wf / n_wf,
+                        'tflops': fl_wf / (ms_wf * 1e-3) / 1e12}
+                if sn:
+                    out['roofline_small_layers'] = {
+                        'kernel': 'the same kernels on the 1-D chains (fused_mlp.Stack1dFn): P = 256 .. 1024 '
+                                  'positions per scene, one or two tiles per workgroup',
+                        'bound': 'latency', 'launches_per_step': per_step(sn), 'ms_per_step': per_step(sms),
+                        'avg_launch_us': 1e3 * sms / sn, 'tflops': sfl / (sms * 1e-3) / 1e12}
+                # the same FLOPs against the whole step (everything that is not a GEMM counts as lost)
+                step_tf = per_step(fl_l + fl_w + fl_wf + sfl) / (ms_per_step * 1e-3) / 1e12
+                out['roofline_step'] = {'bound': 'mfma', 'achieved': step_tf, 'peak': MFMA_F32_PEAK_TFLOPS,
+                                        'unit': 'TFLOP/s', 'frac': step_tf / MFMA_F32_PEAK_TFLOPS,
+                                        'native_gemm_flop_per_step': per_step(fl_l + fl_w + fl_wf + sfl)}
+            else:
+                out['roofline'] = None
+            out['roofline_streaming'] = [e for e in (
+                _stream('nesie::bn_pool_bwd_reduce_kernel + bn_pool_bwd_apply_kernel<16> (SA1 MLP tail, '
+                        'x (B,128,2048,64))', pool_bwd_timer.mean_ms(), 2, big * 4,
+                        extra=3 * pooled_bytes + pooled_bytes // 4),
+                _stream('nesie::bn_bwd_reduce_kernel + bn_bwd_apply_kernel<relu> (B,64,2048,64)',
+                        bn_bwd_timer.mean_ms(), 5, mid * 4),
+                _stream('nesie::bn_bwd_apply_kernel<relu> from the input-gradient kernel\'s partials '
+                        '(B,64,2048,64): read da, z; write dz', bn_apply_timer.mean_ms(), 3, mid * 4)) if e]
+            rounds = 2047
+            out['roofline_latency_bound'] = {
+                'kernel': 'nesie::fps_pruned_kernel<16> (D-FPS 40000->2048: 2047 DEPENDENT rounds, one '
+                          '1024-thread workgroup per scene; longest single launch, overlapped with the '
+                          'previous step on a side stream in graph mode)',
+                'bound': 'latency', 'achieved': fps_ms * 1e3 / rounds if fps_ms else None,
+                'unit': 'us/round', 'rounds': rounds, 'avg_launch_ms': fps_ms,
+                # what a round re-reads: one 20-byte record per bucket test (625 buckets) + the ~12 active
+                # buckets of 64 points x 16 B from L2 + their running minima from LDS
+                'on_chip_bytes_per_round': 625 * 20 + 12 * 64 * (16 + 4),
+                'compulsory_hbm_bytes_per_launch': alg_bytes, 'peak': None, 'frac': None, 'traffic': None}
         if gate is not None:
             out['parity_gate'] = gate
         if args.loss_trace:
             out['loss_trace'] = [float(t) for t in trace]
-        if args.other_workloads and world == 1 and args.workload == 'pretrain' and args.batch == 8 and args.graph:
+        if args.full and args.other_workloads and world == 1 and args.workload == 'pretrain' and args.batch == 8 and args.graph:
             # configs[3] / [4] in front of the driver: free the headline's model, graphs and pools first
             import gc
             step = model = bucket = loss = None
@@ -1211,7 +1239,7 @@ def main():
             torch.cuda.empty_cache()
             out['other_workloads'] = [other_workload(device, 'semi', 8, 5, 2, gate=bool(args.parity_gate)),
                                       other_workload(device, 'saqe', 16, 5, 2, gate=bool(args.parity_gate))]
-        if args.cpu_baseline and world == 1:
+        if args.full and args.cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(args.cpu_batch, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -421,7 +421,7 @@ def test_bare_bench_command_starts_its_own_ranks(workload, batch):
     assert res['config']['global_batch'] == 2 * batch and res['value'] > 0
 
 
-def test_rccl_all_reduce_runs_between_the_graph_replays_on_one_gpu():
+def test_rccl_all_reduce_runs_between_the_graph_replays_on_one_gpu(tmp_path):
     """RCCL itself under the captured step: ``bench.py --gpus 1`` with NESIE_FORCE_PG=1 builds a
     world_size = 1 ``nccl`` (= RCCL) process group, so dp.SegmentedAllReduce really launches both
     gradient all-reduces on the communication stream -- the head's segment between the g1a and g1b
@@ -432,11 +432,14 @@ def test_rccl_all_reduce_runs_between_the_graph_replays_on_one_gpu():
     it was still being written, an update that did not wait for the exchange (the reference's
     collective is NCCL through torch.distributed: train.py:132-139,
     nesie-votenet-scannet-train-010.py:143).  Children are fresh processes; nothing that touched the
-    GPU is re-executed."""
+    GPU is re-executed.  Both runs also write their last step's outputs (``--dump-outputs``): the
+    same arrays, bit for bit, and the dumped loss is the trajectory's last entry."""
     import json
     import os
     import subprocess
     import sys
+
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = {k: v for k, v in os.environ.items()
             if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'NESIE_DIST_BACKEND', 'NESIE_FORCE_PG')}
@@ -447,7 +450,8 @@ def test_rccl_all_reduce_runs_between_the_graph_replays_on_one_gpu():
                                                      MASTER_PORT='29541'))):
         out = _run_children(
             [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '47', '--warmup', '3',
-             '--batch', '2', '--cpu-baseline', '0', '--parity-gate', '0', '--loss-trace', '1'],
+             '--batch', '2', '--cpu-baseline', '0', '--parity-gate', '0', '--loss-trace', '1',
+             '--dump-outputs', str(tmp_path / name)],
             dict(base, **extra))
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -461,6 +465,12 @@ def test_rccl_all_reduce_runs_between_the_graph_replays_on_one_gpu():
     assert len(a) == len(b) == 50 and all(v == v and v > 0 for v in b)
     assert a == b, [(i, x, y) for i, (x, y) in enumerate(zip(a, b)) if x != y][:5]
     assert a[-1] < a[0]                                   # ... and the replayed step trains
+    dumps = {n: {k: np.load(tmp_path / n / f'{k}.npy') for k in ('loss', 'params', 'grads', 'buffers')}
+             for n in runs}
+    for k, v in dumps['plain'].items():
+        assert v.dtype == np.float32 and np.array_equal(v, dumps['rccl'][k]), k
+    assert float(dumps['plain']['loss']) == a[-1]
+    assert dumps['plain']['params'].size == dumps['plain']['grads'].size > 0
     print('loss trajectory with / without the RCCL group: first', a[:3], b[:3], 'last', a[-1], b[-1],
           'largest gap', max(abs(x - y) / max(1.0, abs(x)) for x, y in zip(a, b)))
 
