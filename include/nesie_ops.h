@@ -506,6 +506,22 @@ int nesie_points_in_boxes_count(int b, int boxes_num, int pts_num, const float *
 int nesie_boxes_overlap_bev(int num_a, const float *boxes_a, int num_b, const float *boxes_b,
                             float *ans_overlap, void *stream);
 
+/* iou3d_cuda.nms_gpu / nms_normal_gpu (ops/iou3d/src/iou3d.cpp:95-200, iou3d_kernel.cu:244-345)
+ * over s independent segments in one fixed sequence of launches, without a host round trip.
+ *   boxes (n,5) f32 (x1, y1, x2, y2, ry), scores (n) f32, valid (n) u8 or NULL (rows with
+ *   valid == 0 take no part), offsets (s+1) i32 on the device: segment t is rows
+ *   [offsets[t], offsets[t+1]); max_seg: a bound on every segment's length, <= 8192
+ *   (NESIE_ERR_INVALID_ARG above; a segment longer than max_seg reports count -1).
+ *   rotated 1: iou_bev (rotated overlap / fmaxf(sa + sb - ov, 1e-8)); 0: iou_normal (ry
+ *   ignored).  A box is suppressed when iou > thr.
+ *   keep (n) i32: the kept input rows of segment t at keep[offsets[t] .. + count[t]), in
+ *   descending score order (equal scores by ascending row, NaN after every number);
+ *   count (s) i32.
+ *   workspace: n * (8 * ceil(max_seg / 64) + 24) bytes, device memory. */
+int nesie_bev_nms(int n, int s, int max_seg, const float *boxes, const float *scores,
+                  const uint8_t *valid, const int *offsets, float thr, int rotated, int *keep,
+                  int *count, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- input side ---------------------------------------------------------- */
 
 /* One training batch from HBM-resident scenes: the reference's per-sample CPU pipeline

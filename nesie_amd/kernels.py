@@ -481,6 +481,21 @@ class HipKernels(_BNPoolMixin):
             _lib.call("nesie_boxes_overlap_bev", n, _ptr(boxes_a), m, _ptr(boxes_b),
                       _ptr(ans_overlap), _stream(boxes_a))
 
+    def bev_nms(self, boxes, scores, valid, offsets, max_seg, thr, rotated, keep, count, ws):
+        """(n,5) (x1,y1,x2,y2,ry), scores (n), valid (n) u8 or None, offsets (S+1) i32 ->
+        keep (n) i32 (kept rows of segment t from offsets[t], best first), count (S) i32."""
+        _check(boxes, scores, offsets, keep, count, ws); _f32(boxes, scores); _i32(offsets, keep, count)
+        n, s = scores.numel(), count.numel()
+        assert tuple(boxes.shape) == (n, 5) and offsets.numel() == s + 1 and keep.numel() == n
+        if valid is not None:
+            _check(valid)
+            assert valid.dtype == torch.uint8 and valid.numel() == n
+        with torch.cuda.device(boxes.device):
+            _lib.call("nesie_bev_nms", n, s, int(max_seg), _ptr(boxes), _ptr(scores),
+                      0 if valid is None else _ptr(valid), _ptr(offsets), float(thr),
+                      1 if rotated else 0, _ptr(keep), _ptr(count), _ptr(ws),
+                      ws.numel() * ws.element_size(), _stream(boxes))
+
     def scene_assemble(self, pool, height, choices, xform, out):
         """pool (R,3), height (R), choices (B,n) i32 rows of the pool, xform (B,20) -> out (B,n,4)."""
         _check(pool, height, choices, xform, out); _f32(pool, height, xform, out); _i32(choices)

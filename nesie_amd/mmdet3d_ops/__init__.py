@@ -13,7 +13,7 @@ from .interpolate import blend_conv, blend_conv_bn, three_interpolate, three_int
 from .pointnet_modules import (ConvModule, PointFPModule, PointSAModule, PointSAModuleMSG,
                                PointwiseConv1d, PointwiseConv2d, build_sa_module,
                                pointwise_conv)
-from .iou3d import boxes_overlap_bev
+from .iou3d import batched_nms_bev, boxes_iou_bev, boxes_overlap_bev, nms_gpu, nms_normal_gpu
 from .roiaware_pool3d import points_in_boxes_batch, points_in_boxes_count
 from .rotated_iou import cal_iou_3d, sort_v
 
@@ -23,6 +23,7 @@ _HOT = [
     'GroupAll', 'QueryAndGroup', 'PointSAModule', 'PointSAModuleMSG', 'PointFPModule',
     'points_in_boxes_batch', 'Points_Sampler', 'build_sa_module', 'cal_iou_3d', 'sort_v',
     'ConvModule', 'boxes_overlap_bev', 'points_in_boxes_count',
+    'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',

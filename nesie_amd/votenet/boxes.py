@@ -1,7 +1,11 @@
 """The slice of ``mmdet3d/core/bbox/structures/depth_box3d.py`` (+ ``base_box3d.py``) the
 training step and the test path touch: gravity centres (:42-48), ``points_in_boxes``
 (:251-277) with the depth->LiDAR frame change of ``box_3d_mode.py:124-127``, ``corners``
-(:50-89), indexing, and the 3-D ``overlaps`` of evaluation (base_box3d.py:355-438)."""
+(:50-89), indexing, the 3-D ``overlaps`` of evaluation (base_box3d.py:355-438), and the
+``flip`` / ``scale`` / ``cat`` / ``clone`` of test-time augmentation (depth_box3d.py:176-199,
+base_box3d.py:215-222, 292-339)."""
+import math
+
 import torch
 
 from ..kernels import injected_backend
@@ -23,6 +27,8 @@ def depth_to_lidar_boxes(boxes):
 class DepthInstance3DBoxes:
     """(T,7) boxes in the depth frame, (x, y, z_bottom, dx, dy, dz, yaw)."""
 
+    with_yaw = True
+
     def __init__(self, tensor, box_dim=7, with_yaw=True, origin=(0.5, 0.5, 0)):
         tensor = torch.as_tensor(tensor, dtype=torch.float32)
         if tensor.numel() == 0:
@@ -43,6 +49,40 @@ class DepthInstance3DBoxes:
         out = DepthInstance3DBoxes.__new__(DepthInstance3DBoxes)
         out.tensor = self.tensor.to(device)
         return out
+
+    def clone(self):
+        out = DepthInstance3DBoxes.__new__(DepthInstance3DBoxes)
+        out.tensor = self.tensor.clone()
+        out.with_yaw = self.with_yaw
+        return out
+
+    @classmethod
+    def cat(cls, boxes_list):
+        """One set of boxes from a list (never sharing storage with the inputs)."""
+        assert isinstance(boxes_list, (list, tuple))
+        if len(boxes_list) == 0:
+            return cls(torch.empty(0))
+        out = cls.__new__(cls)
+        out.tensor = torch.cat([b.tensor for b in boxes_list], dim=0)
+        out.with_yaw = boxes_list[0].with_yaw
+        return out
+
+    def flip(self, bev_direction='horizontal'):
+        """In place: horizontal negates x (yaw -> pi - yaw), vertical negates y (yaw -> -yaw)."""
+        assert bev_direction in ('horizontal', 'vertical')
+        if bev_direction == 'horizontal':
+            self.tensor[:, 0::7] = -self.tensor[:, 0::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6] + math.pi
+        else:
+            self.tensor[:, 1::7] = -self.tensor[:, 1::7]
+            if self.with_yaw:
+                self.tensor[:, 6] = -self.tensor[:, 6]
+
+    def scale(self, scale_factor):
+        """In place: centres and sizes times ``scale_factor``."""
+        self.tensor[:, :6] *= scale_factor
+        self.tensor[:, 7:] *= scale_factor
 
     def new_box(self, data):
         return DepthInstance3DBoxes(torch.as_tensor(data, dtype=torch.float32,

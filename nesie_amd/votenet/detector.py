@@ -136,6 +136,27 @@ class VoteNet(nn.Module):
                                                           img_metas)
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
+    def aug_test(self, points, img_metas, imgs=None, rescale=False):
+        """Test with augmentation (detectors/votenet.py:85-105, votenet_nesie.py:573-595):
+        ``points`` holds one one-sample list per view, ``img_metas`` one one-element list of
+        metas per view (pcd_scale_factor, pcd_horizontal_flip, pcd_vertical_flip;
+        ``nesie_amd.tta.tta_views`` makes both).  The A views run as ONE batch of A scenes
+        (the reference runs a forward per view), then the merge of ``merge_aug_bboxes_3d``
+        on the device.  -> [dict of host results]."""
+        from ..tta import merge_detect_tensors
+        views = [torch.stack(list(p)) if isinstance(p, (list, tuple)) else p for p in points]
+        assert all(v.shape[0] == 1 for v in views), 'aug_test supports one sample per view'
+        points_cat = torch.cat(views, 0)
+        cfg = self.test_cfg if isinstance(self.test_cfg, dict) else vars(self.test_cfg)
+        with torch.no_grad():
+            x = self.extract_feat(points_cat)
+            bbox_preds = self.bbox_head(x, cfg['sample_mod'])
+            tensors = self.bbox_head.detect_tensors(points_cat, bbox_preds,
+                                                    cfg.get('use_iou_for_nms', True))
+            merged = merge_detect_tensors(tensors, img_metas, cfg,
+                                          bool(cfg.get('per_class_proposal', False)))
+        return [merged]
+
     def graphed_simple_test(self, batch, num_points, feat_dim=4, device=None):
         """-> callable(points, img_metas=None) with ``simple_test``'s results, the device half
         (backbone, head, score fusion, point counts, NMS) captured once as a hipGraph for a fixed
