@@ -487,15 +487,13 @@ static int bn_check(const char *W, int b, int c, long long p, const void *ws, si
 }
 
 // Non-temporal accesses for tensors that cannot stay in the 256 MB Infinity Cache anyway.
-// NESIE_NT_MB=<n>: threshold in MB (0 = never), a measurement aid.
 namespace nesie {
-bool stream_nt(long long bytes, int family) {
-  static const long long mb = [] { const char *e = getenv("NESIE_NT_MB"); return e ? atoll(e) : 192ll; }();
-  static const int mask = [] { const char *e = getenv("NESIE_NT_MASK"); return e ? atoi(e) : 3; }();
-  return mb > 0 && (mask & family) && bytes >= (mb << 20);
+bool stream_nt(long long bytes) {
+  constexpr long long mb = 192;
+  return bytes >= (mb << 20);
 }
 }  // namespace nesie
-static bool bn_use_nt(long long elements) { return nesie::stream_nt(elements * 4, 1); }
+static bool bn_use_nt(long long elements) { return nesie::stream_nt(elements * 4); }
 
 extern "C" int nesie_bn_relu_forward(int b, int c, long long p, const float *x,
                                      const float *gamma, const float *beta,
@@ -524,7 +522,7 @@ extern "C" int nesie_bn_relu_forward(int b, int c, long long p, const float *x,
   NESIE_REQUIRE(!pre_partial || (pre_nslice >= 1 && !row_bias), W);
   if (!pre_partial)
     hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(BN_BLOCK), 0, s, c, p, sp, x, row_bias, group,
-                       partial, nesie::stream_nt((long long)b * c * p * 4, 8) ? 1 : 0);
+                       partial, 0);
   // the producer's partials are unshifted sums: no shift element (x = NULL in the finalize)
   const BnFwdFin fin{pre_partial ? pre_nslice : nslice, (double)b * (double)p,
                      pre_partial ? nullptr : x, p, row_bias, group,
@@ -665,8 +663,7 @@ extern "C" int nesie_bn_relu_maxpool_forward(int b, int c, int m, int ns, const 
   const int sp = bn_sp(p), nslice = b * sp;
   float *partial = (float *)workspace;
   hipLaunchKernelGGL(bn_stats_kernel, dim3(sp, c, b), dim3(BN_BLOCK), 0, s, c, p, sp, x,
-                     (const float *)nullptr, 1, partial,
-                     nesie::stream_nt((long long)b * c * p * 4, 8) ? 1 : 0);
+                     (const float *)nullptr, 1, partial, 0);
   const BnFwdFin fin{nslice, (double)b * (double)p, x, p, nullptr, 1, partial, gamma, beta,
                      running_mean, running_var, momentum, eps, save_mean, save_invstd, fwd_coef};
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(64), 0, s, fin, c);
@@ -676,7 +673,7 @@ extern "C" int nesie_bn_relu_maxpool_forward(int b, int c, int m, int ns, const 
   const dim3 grid((unsigned)cdiv((long long)m * lpr, 256), (unsigned)(b * c));
 #define L(N) hipLaunchKernelGGL(bn_pool_fwd_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
                                 (const float4 *)x, fwd_coef, pooled, argmax, nt)
-  const int nt = stream_nt(rows * ns * 4, 2) ? 1 : 0;
+  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
   if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
   else if (lpr == 8) L(8); else L(16);
 #undef L
@@ -714,7 +711,7 @@ extern "C" int nesie_bn_relu_maxpool_backward(int b, int c, int m, int ns,
 #define L(N) hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
                                 (const float4 *)x, grad_pooled, pooled, argmax, fwd_coef, coef, \
                                 (float4 *)dx, nt)
-  const int nt = stream_nt(rows * ns * 4, 2) ? 1 : 0;
+  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
   if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
   else if (lpr == 8) L(8); else L(16);
 #undef L
@@ -788,7 +785,7 @@ extern "C" int nesie_affine_relu_maxpool_forward(int b, int c, int m, int ns, co
   NESIE_REQUIRE((long long)b * c <= 65535 && (long long)m * lpr < (1ll << 30), W);
   const dim3 grid((unsigned)cdiv((long long)m * lpr, 256), (unsigned)(b * c));
   hipStream_t s = (hipStream_t)stream;
-  const int nt = stream_nt(rows * ns * 4, 2) ? 1 : 0;
+  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
 #define L(N) hipLaunchKernelGGL(bn_pool_fwd_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
                                 (const float4 *)x, coef, pooled, argmax, nt)
   if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);

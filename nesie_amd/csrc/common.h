@@ -33,9 +33,9 @@ inline int check_launch(const char *what) {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// true when a tensor of this size should be streamed with non-temporal accesses (bn.hip)
-// family: 1 = norm passes, 2 = pooling passes, 4 = blend (NESIE_NT_MASK selects; default 3: same-box A/B showed the blend stores neutral)
-bool stream_nt(long long bytes, int family);
+// true when a tensor of this size should be streamed with non-temporal accesses (bn.hip): the norm
+// and pooling passes ask; the blend stores (same-box A/B: neutral) and the norm statistics do not
+bool stream_nt(long long bytes);
 
 // Squared distance in the canonical, contraction-free form
 // ((dx*dx) + (dy*dy)) + (dz*dz)   (SURVEY.md appendix A.0).

@@ -610,13 +610,7 @@ static int fps_launch(int b, int n, int m, const float *xyz, float *temp, int *i
                       void *workspace, size_t workspace_bytes, void *stream);
 
 // running-min distances in LDS (and the spatial index left behind): n floats must fit the CU
-static bool fps_lds_mode(int n) {
-  static const int enabled = [] {
-    const char *e = getenv("NESIE_FPS_LDS");
-    return e ? atoi(e) : 1;
-  }();
-  return enabled && n <= FPS_INDEX_MAX_N;
-}
+static bool fps_lds_mode(int n) { return n <= FPS_INDEX_MAX_N; }
 
 extern "C" int nesie_fps_leaves_index(int b, int n) {
   // (a fused distance form runs on the plain kernel, which builds no index)
@@ -666,42 +660,24 @@ static int fps_launch(int b, int n, int m, const float *xyz, float *temp, int *i
       ((uintptr_t)workspace & 15) == 0) {
     float4 *wp = (float4 *)workspace;
     unsigned *wo = (unsigned *)((char *)workspace + (size_t)b * n * 16);
-    static const int nw = [] {
-      const char *e = getenv("NESIE_FPS_WAVES");
-      return e ? atoi(e) : 16;
-    }();
-    const bool lds_temps = fps_lds_mode(n);
     const size_t lt_bytes = (size_t)n * 4 > (FPS_CELLS + 1024) * 4 ? (size_t)n * 4 : (FPS_CELLS + 1024) * 4;
-    const bool lds_ok = lds_temps;
-#define PRUNED(NWV)                                                                              \
+#define PRUNED_LDS(FULL)                                                                         \
   do {                                                                                           \
-    if (lds_ok && n % 64 == 0) {                                                                 \
-      auto kern = fps_pruned_kernel<NWV, true, true>;                                            \
-      static bool attr = false;                                                                  \
-      if (!attr) {                                                                               \
-        (void)hipFuncSetAttribute((const void *)kern,                                            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160768);           \
-        attr = true;                                                                             \
-      }                                                                                          \
-      hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lt_bytes, s, n, m, xyz, temp, idx, wp, wo); \
-    } else if (lds_ok) {                                                                         \
-      auto kern = fps_pruned_kernel<NWV, true, false>;                                           \
-      static bool attr = false;                                                                  \
-      if (!attr) {                                                                               \
-        (void)hipFuncSetAttribute((const void *)kern,                                            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160768);           \
-        attr = true;                                                                             \
-      }                                                                                          \
-      hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lt_bytes, s, n, m, xyz, temp, idx, wp, wo); \
-    } else {                                                                                     \
-      hipLaunchKernelGGL((fps_pruned_kernel<NWV, false, false>), grid, dim3(NWV * 64), 0, s, n, m, xyz, \
-                         temp, idx, wp, wo);                                                     \
+    auto kern = fps_pruned_kernel<16, true, FULL>;                                               \
+    static bool attr = false;                                                                    \
+    if (!attr) {                                                                                 \
+      (void)hipFuncSetAttribute((const void *)kern,                                              \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160768);             \
+      attr = true;                                                                               \
     }                                                                                            \
+    hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lt_bytes, s, n, m, xyz, temp, idx, wp, wo);    \
   } while (0)
-    if (nw == 16) PRUNED(16);
-    else if (nw == 8) PRUNED(8);
-    else PRUNED(4);
-#undef PRUNED
+    if (!fps_lds_mode(n))
+      hipLaunchKernelGGL((fps_pruned_kernel<16, false, false>), grid, dim3(16 * 64), 0, s, n, m, xyz,
+                         temp, idx, wp, wo);
+    else if (n % 64 == 0) PRUNED_LDS(true);
+    else PRUNED_LDS(false);
+#undef PRUNED_LDS
     return check_launch(W);
   }
   if (n <= 64) REG(64, 1);

@@ -777,8 +777,7 @@ int launch_inverted_index(int b, int n, long long e_total, const int *idx, int *
   NESIE_REQUIRE(b >= 0 && n >= 1 && e_total >= 0 && e_total < (1ll << 31), W);
   if (b == 0) return NESIE_OK;
   NESIE_REQUIRE(idx && order && sources && scratch, W);
-  static const int stable_on = getenv("NESIE_INDEX_STABLE") ? atoi(getenv("NESIE_INDEX_STABLE")) : 1;   // A/B switch
-  if (stable_on && n <= II_STABLE_N) {               // stable counting sort: ascending runs without a ranking pass
+  if (n <= II_STABLE_N) {               // stable counting sort: ascending runs without a ranking pass
     const size_t lds = ((size_t)II_WAVES * n + II_BLOCK) * sizeof(int);
     static bool attr = false;
     if (!attr) {

@@ -135,7 +135,7 @@ extern "C" int nesie_group_max_pool_forward(long long rows, int nsample, const f
   hipStream_t s = (hipStream_t)stream;
 #define L(N) hipLaunchKernelGGL(group_max_fwd_kernel<N>, grid, dim3(256), 0, s, rows, \
                                 (const float4 *)x, out, argmax, nt)
-  const int nt = stream_nt(rows * nsample * 4, 2) ? 1 : 0;
+  const int nt = stream_nt(rows * nsample * 4) ? 1 : 0;
   if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
   else if (lpr == 8) L(8); else L(16);
 #undef L
@@ -157,7 +157,7 @@ extern "C" int nesie_group_max_pool_backward(long long rows, int nsample,
   hipStream_t s = (hipStream_t)stream;
 #define L(N) hipLaunchKernelGGL(group_max_bwd_kernel<N>, grid, dim3(256), 0, s, rows, \
                                 grad_out, argmax, (float4 *)grad_x, nt)
-  const int nt = stream_nt(rows * nsample * 4, 2) ? 1 : 0;
+  const int nt = stream_nt(rows * nsample * 4) ? 1 : 0;
   if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
   else if (lpr == 8) L(8); else L(16);
 #undef L

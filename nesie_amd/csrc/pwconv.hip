@@ -12,7 +12,6 @@ namespace nesie {
 // (K sub-tile / 16, sub-tiles along K, row waves, column waves, 16-row sets per wave)
 PW_GEOM_DECL(4, 1, 4, 1, 1)    // K <= 64,  Cout <= 64   (HBM-bound: small workgroups, up to four per CU)
 PW_GEOM_DECL(4, 1, 4, 1, 2)    // K <= 64,  Cout <= 128
-PW_GEOM_DECL(4, 1, 8, 1, 1)    // K <= 64,  Cout <= 128  (A/B: NESIE_PW_K64=8)
 PW_GEOM_DECL(8, 1, 4, 1, 1)    // K <= 128, Cout <= 64
 PW_GEOM_DECL(8, 1, 8, 1, 1)    // K <= 128, Cout <= 128
 PW_GEOM_DECL(9, 1, 8, 1, 1)    // K <= 144
@@ -136,9 +135,7 @@ static bool pw_geometry(int k, int cout, PwGeom *o) {
   // two-team ping-pong workgroup.
   o->nhalf = (cout + 127) / 128;   // 128-row workgroups per tile
   if (o->kt16 == 4) {
-    static const int k64 = [] { const char *e = getenv("NESIE_PW_K64"); return e ? atoi(e) : 4; }();
     o->wr = 4; o->wc = 1; o->rw = cout <= 64 ? 1 : 2;
-    if (k64 == 8 && cout > 64) { o->wr = 8; o->rw = 1; }                       // A/B switch
   } else if (cout <= 64 && o->kt16 == 8 && o->kh == 1) {
     o->wr = 4; o->wc = 1; o->rw = 1;
   } else {
@@ -169,10 +166,7 @@ extern "C" int nesie_pw_supported(int k, int cout, long long p) {
 // workgroups per weight group of a launch
 static int pw_groups(const PwGeom &g, int nb, int ng, long long p) {
   const long long tiles = (long long)(nb / ng) * cdiv(p, g.pt);
-  // NESIE_PW_ROUNDS (A/B, default 1): R shorter rounds of workgroups instead of one -- a CU that is
-  // not available to this launch (a long-lived tenant of another stream) then delays 1/R of it
-  static const int rounds = [] { const char *e = getenv("NESIE_PW_ROUNDS"); return e ? atoi(e) : 1; }();
-  long long nwg = (long long)cu_count() * g.per_cu * (rounds > 0 ? rounds : 1) / (ng * g.nhalf);
+  long long nwg = (long long)cu_count() * g.per_cu / (ng * g.nhalf);
   if (nwg < 1) nwg = 1;
   if (nwg > tiles) nwg = tiles;
   // several row blocks per tile: a grid that is a multiple of 8 * nhalf lets the row blocks of a
@@ -259,10 +253,8 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
   a.bn_z = bn_z; a.bnz_bs = bnz_bstride; a.bn_coef = bn_coef; a.bn_part = bn_part;
   a.stamps = nullptr;
   a.k4_w = k4_w; a.k4_gpart = k4_gpart;
-  static const int w_stage = [] { const char *e = getenv("NESIE_PW_WSTAGE"); return e ? atoi(e) : 1; }();
-  a.w_stage = w_stage;
-  static const int rev_fwd = [] { const char *e = getenv("NESIE_PW_REV_FWD"); return e ? atoi(e) : 3; }();   // A/B: bit 0 forward products, bit 1 input gradients
-  a.rev = ((bn_z ? rev_fwd & 2 : rev_fwd & 1) != 0) ? walk_dir((long long)nb * (k4_in ? 4 : k) * p * 4) : 0;     // (a big operand is read last tile first: nesie_lib.hip)
+  a.w_stage = 1;
+  a.rev = walk_dir((long long)nb * (k4_in ? 4 : k) * p * 4);     // (a big operand is read last tile first: nesie_lib.hip)
 #ifdef PW_STAMP
   a.stamps = g_pw_stamps;
 #endif
@@ -282,7 +274,7 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
 #ifdef PW_DEV
   G(8, 2, 8, 1, 1); G(8, 1, 8, 1, 1);
 #else
-  G(4, 1, 4, 1, 1); G(4, 1, 4, 1, 2); G(4, 1, 8, 1, 1); G(8, 1, 4, 1, 1); G(8, 1, 8, 1, 1);
+  G(4, 1, 4, 1, 1); G(4, 1, 4, 1, 2); G(8, 1, 4, 1, 1); G(8, 1, 8, 1, 1);
   G(9, 1, 8, 1, 1); G(8, 2, 8, 1, 1); G(9, 2, 8, 1, 1); G(8, 4, 8, 1, 1);
 #endif
 #undef G

@@ -163,7 +163,7 @@ struct PwFwd {
   int tiles_per_batch, nwg_g, nhalf;       // nhalf: workgroups per tile along Cout
   int xcd_map;         // the nhalf workgroups of a tile stream sit on ONE XCD (grid % (8 nhalf) == 0)
   const float2 *sp_ent; int sp_ns_shift, sp_groups;   // PW_SPARSE*: entries, log2(ns), groups per batch element
-  int w_stage;         // 1: row-major weights come in through LDS (NESIE_PW_WSTAGE=0: lane loads, A/B switch)
+  int w_stage;         // 1: row-major weights come in through LDS (0: lane loads)
   int rev;             // 1: the tile stream runs from the LAST tile of the group to the first (big operands: nesie_lib.hip)
   const float *k4_w;   // PW_K4IN / PW_K4Z: W0 (64, 4) row-major
   float *k4_gpart;     // PW_K4Z: [ng * cout][nslots][4]

@@ -503,13 +503,11 @@ static int rd_flush(hipStream_t s) {
 }
 
 // workgroups per weight group: one per CU; TWO per CU where a block's tiles (<= 74 KB of LDS) and
-// registers (<= 128) allow it (NESIE_WGRAD_PER_CU=1: A/B switch)
+// registers (<= 128) allow it
 static int pw_wgrad_nwg(int nb, int ng, long long p, int co, int cw, bool bnb = false) {
-  static const int per_cu_max = getenv("NESIE_WGRAD_PER_CU") ? atoi(getenv("NESIE_WGRAD_PER_CU")) : 2;
   // (the fused norm-backward variants need 146-150 VGPRs at 128 x 128: one workgroup per CU there)
-  const int per_cu = (co <= 128 && cw <= (bnb ? 64 : 128) && per_cu_max >= 2) ? 2 : 1;
-  static const int rounds = [] { const char *e = getenv("NESIE_WGRAD_ROUNDS"); return e ? atoi(e) : 1; }();   // A/B
-  long long nwg = (long long)cu_count() * per_cu * (rounds > 0 ? rounds : 1) / ng;
+  const int per_cu = (co <= 128 && cw <= (bnb ? 64 : 128)) ? 2 : 1;
+  long long nwg = (long long)cu_count() * per_cu / ng;
   const long long tiles = (long long)(nb / ng) * (p / 32);
   if (nwg > tiles) nwg = tiles;
   return nwg < 1 ? 1 : (int)nwg;
@@ -533,8 +531,7 @@ extern "C" int nesie_pw_wgrad_supported(int co, int ci, long long p) {
 // weight group and more than one whole-product column block's worth of output.
 constexpr int TILED_B = 64, TILED_MAX_TILES = 1024;
 static bool pw_wgrad_tiled(int nb, int ng, int co, int ci, long long p) {
-  static const int on = getenv("NESIE_WGRAD_TILED") ? atoi(getenv("NESIE_WGRAD_TILED")) : 1;   // A/B switch
-  if (!on || nb <= 0 || ng <= 0 || nb % ng || p <= 0 || p % 32 || ci < 9 || ci > 1024 || co < 1 || co > 1024) return false;
+  if (nb <= 0 || ng <= 0 || nb % ng || p <= 0 || p % 32 || ci < 9 || ci > 1024 || co < 1 || co > 1024) return false;
   const long long tiles = (long long)(nb / ng) * (p / 32);
   return tiles <= TILED_MAX_TILES && (long long)co * ci >= 128 * 192;
 }
@@ -631,8 +628,7 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
   NESIE_REQUIRE((long long)(nb / ng) * (p / 32) < (1ll << 30), W);     // (32-bit tile cursor)
   const float lo0 = x_relu ? 0.f : -__builtin_inff();
   // dY is the tensor a launch has just written: a big one is read last tile first (nesie_lib.hip)
-  static const int rev_on = [] { const char *e = getenv("NESIE_PW_REV_WGRAD"); return e ? atoi(e) : 1; }();   // A/B
-  const int rev = rev_on ? walk_dir((long long)nb * co * p * 4) : 0;
+  const int rev = walk_dir((long long)nb * co * p * 4);
   if (tiled_mode) {
     const int nwg = pw_wgrad_tiled_nwg(nb, ng, co, ci, p);
     const int nrb = cdiv(co, TILED_B), ncb = cdiv(ci, TILED_B);

@@ -18,7 +18,6 @@ re-derived with the same fused multiply-add the forward's operand load used).
 Same function as the module-by-module path (which stays the CPU checker's and serves shapes the
 kernels are not built for); differences are fp32 summation order and fma-vs-mul/add rounding.
 """
-import os as _os
 
 import torch
 from torch.autograd import Function
@@ -29,23 +28,19 @@ from ..kernels import backend_for
 
 # Tests flip this to obtain the module-by-module evaluation of the same network on the device.
 ENABLED = True
+# Plain constants like ENABLED, not settings: tests flip them to compare the same model both ways.
+# SA1_K4: SA1's first activation (4 -> 64 over 10^6 positions, 268 MB) is rebuilt from the 17 MB input
+# wherever it is an operand instead of being stored (include/nesie_ops.h, round 5).
+# FOLD_NORM_BWD: the BatchNorm + ReLU backward's apply pass runs inside the weight gradient instead
+# of as its own launch (nesie_bn_relu_backward_apply) in front of it.
+SA1_K4 = True
+FOLD_NORM_BWD = True
 
 # Ownership hand-over of a freshly allocated gradient buffer between MiniTailFn.backward and
 # MiniHeadFn.backward: the producer marks the TENSOR OBJECT (an attribute, not its address -- an
 # address outlives the tensor in the caching allocator and could be handed to an unrelated gradient
 # later); whatever autograd builds from it for a second consumer is a new object without the mark.
 _OWNED_MARK = '_nesie_fresh_grad'
-
-
-# Layers wider than one workgroup's accumulators (the 1-D chains' 256 x 256 / 256 x 512 at 8 x 1024
-# positions) ran in nesie_pw_wgrad as column blocks, one launch + one partial reduction each; at
-# these sizes (one 32-position tile per workgroup, 32 MB of partials per block) a transposed copy +
-# one rocBLAS GEMM was faster (553 / 557 vs 548 / 548 scenes/s, same-box A/B), so round 3 kept
-# rocBLAS there.  Round 4: such shapes run TILED (``pw_wgrad_tiled``: one launch over 64 x 64 blocks
-# of the product, split-K with a fixed-order reduction, 8 MB of partials) -- no transposed copies,
-# no rocBLAS.  NESIE_WGRAD_WIDE=1 forces the native kernel for every shape it supports,
-# NESIE_WGRAD_TILED=0 switches the tiled mode off (A/B).
-WIDE_WGRAD = _os.environ.get('NESIE_WGRAD_WIDE', '0') != '0'
 
 
 def _dst(slot, like, *shape):
@@ -67,8 +62,10 @@ def _wgrad(backend, dy, x, x_coef, ng=1, slot=None):
     bias) when x_coef (ng * Cin, 4).  ``slot``: the weight's gradient slot (written in place)."""
     nb, co, p = dy.shape
     ci = x.shape[1]
+    # wide products over few positions run tiled; the rest natively while one workgroup's accumulators
+    # hold the whole product (wider layers as column blocks were slower than a transposed copy + rocBLAS)
     if backend.pw_wgrad_tiled(nb, ng, co, ci, p) or (
-            backend.pw_wgrad_supported(co, ci, p) and (WIDE_WGRAD or (ci <= 320 if co <= 128 else ci <= 128))):
+            backend.pw_wgrad_supported(co, ci, p) and (ci <= 320 if co <= 128 else ci <= 128)):
         dw = _dst(slot, dy, ng, co, ci)
         # (a slot of the flat gradient vector is read by nobody before the optimiser: its reduction
         # may wait for the one batched launch at FlatTrainState.collect())
@@ -106,15 +103,6 @@ def _wgrad_aten(backend, dy, x, x_coef, ng):
     return out[0].unsqueeze(0) if ng == 1 else torch.stack(out)
 
 
-# NESIE_FOLD_NORM_BWD=0: A/B switch -- the BatchNorm + ReLU backward's apply pass runs as its own
-# launch (nesie_bn_relu_backward_apply) in front of the weight gradient instead of inside it
-FOLD_NORM_BWD = _os.environ.get('NESIE_FOLD_NORM_BWD', '1') != '0'
-# the pooled last layer of an SA stack without its dense pre-pool tensor (csrc/pool_tail.hip): the
-# forward keeps (pooled, arg-max, raw extremum) only, the backward goes through
-# dZ = sparse + alpha + beta Z.  0: the dense form (A/B switch)
-POOL_TAIL = _os.environ.get('NESIE_POOL_TAIL', '1') != '0'
-
-
 def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_w, ng=1, need_dz=True,
                          slots=(None, None, None)):
     """The backward of relu(bn(z)) given da (its gradient) and the reduction partials the
@@ -145,12 +133,6 @@ def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_
                                    dz.view(b, ng * co, p), dgamma, dbeta)
     dw = _wgrad(backend, dz, src, src_coef, ng=ng, slot=s_w) if need_w else None
     return dz, dw, dgamma, dbeta
-
-
-# SA1's first activation (4 -> 64 over 10^6 positions, 268 MB) is rebuilt from the 17 MB input wherever
-# it is an operand instead of being stored (include/nesie_ops.h, round 5).  0 = store it (A/B switch).
-SA1_K4 = _os.environ.get('NESIE_SA1_K4', '1') != '0'
-SA1_K4_FUSED = _os.environ.get('NESIE_SA1_K4_FUSED', '1') != '0'     # (A/B: 0 = two launches with dZ in between)
 
 
 class SAStackFn(Function):
@@ -184,7 +166,10 @@ class SAStackFn(Function):
             w2 = w.reshape(1, cout, cin)
             src = x3 if l == 0 else ys[-1]
             last = l == L - 1
-            tail = bool(last and l > 0 and POOL_TAIL and backend.pool_tail_supported(cin, cout, P, ns))
+            # the pooled last layer without its dense pre-pool tensor (csrc/pool_tail.hip): the forward
+            # keeps (pooled, arg-max, raw extremum) only, the backward goes through
+            # dZ = sparse + alpha + beta Z; the dense form serves the shapes pool_tail_supported refuses
+            tail = bool(last and l > 0 and backend.pool_tail_supported(cin, cout, P, ns))
             # (tail: the raw output is never written; k4: nor is the first layer's)
             y = None if (tail or (ctx.k4 and l == 0)) else x.new_empty(B, cout, P)
             new_coef = x.new_empty(cout, 4)
@@ -273,21 +258,17 @@ class SAStackFn(Function):
             need_w = ctx.needs_input_grad[3 + 3 * l]
             if ctx.k4 and l == 1:
                 # second layer over the rebuilt first activation: its fused norm backward + weight
-                # gradient, then ONLY the reductions of its input gradient -- they determine the
-                # first layer's norm backward and weight gradient (nesie_k4_first_layer_wgrad)
+                # gradient and ONLY the reductions of its input gradient -- they determine the
+                # first layer's norm backward and weight gradient (nesie_k4_first_layer_wgrad) --
+                # as one launch: the layer's dZ never leaves the chip
                 assert pending is not None
                 w0 = params[0]
                 w0c = w0.reshape(w0.shape[0], c0)
                 dgamma, dbeta = _dst(slots[4], g, cout), _dst(slots[5], g, cout)
                 dw = _dst(slots[3], g, 1, cout, cin)
-                if SA1_K4_FUSED:     # ... both as one launch: the layer's dZ never leaves the chip
-                    part, g_part = backend.pw_wgrad_bn_backward_k4_fused(
-                        pending[0], ys[1], coefs[1], params[4], pending[1], x3, w0c, coefs[0], w2, dw, dgamma, dbeta,
-                        final=slots[3] is not None)
-                else:
-                    backend.pw_wgrad_bn_backward_k4(pending[0], ys[1], coefs[1], params[4], pending[1], x3, w0c,
-                                                    coefs[0], dw, dgamma, dbeta, final=slots[3] is not None)
-                    part, g_part = backend.pw_dgrad_bn_reduce_k4(pending[0], w2.t(), x3, w0c, coefs[0])
+                part, g_part = backend.pw_wgrad_bn_backward_k4_fused(
+                    pending[0], ys[1], coefs[1], params[4], pending[1], x3, w0c, coefs[0], w2, dw, dgamma, dbeta,
+                    final=slots[3] is not None)
                 grads[3], grads[4], grads[5] = dw.view_as(w), dgamma, dbeta
                 dgamma0, dbeta0 = _dst(slots[1], g, cin), _dst(slots[2], g, cin)
                 bnb = backend.pw_bnb_coef(part, coefs[0], params[1], float(B) * float(P), dgamma0, dbeta0)
@@ -997,20 +978,13 @@ class Stack1dFn(Function):
         return (dx, None, None) + tuple(grads)
 
 
-# A/B switch (NESIE_STACK1D, default 31): bit 0 vote module, 1 prediction head, 2 feature
-# propagation, 3 score heads, 4 the prediction head's output convs -- which chains run through Stack1dFn
-STACK1D_MASK = int(_os.environ.get('NESIE_STACK1D', '31'))
-VOTE, PRED, FPROP, HEADS, PRED_OUT = 1, 2, 4, 8, 16   # (PRED_OUT: the prediction head's three output convs)
-
-
-def stack1d_supported(backend, x, shapes, norms, S=1, which=15):
+def stack1d_supported(backend, x, shapes, norms, S=1):
     """True when ``Stack1dFn`` serves the chain: ``shapes`` = [(Cin, Cout), ...], ``norms`` = the
     norm layer (or None) behind each conv; native training BatchNorm1d/2d with a folded ReLU,
     fp32, every forward and input-gradient product inside the built tiles, only the LAST layer
     may come without a norm."""
     from .norm import FusedBNReLU1d, FusedBNReLU2d
-    if not ENABLED or backend.name != 'hip' or x.dtype != torch.float32 or not torch.is_grad_enabled() \
-            or not (STACK1D_MASK & which):
+    if not ENABLED or backend.name != 'hip' or x.dtype != torch.float32 or not torch.is_grad_enabled():
         return False
     P = x.shape[-1] if x.dim() == 3 else x.numel() // (x.shape[0] * x.shape[1])
     for i, ((cin, cout), norm) in enumerate(zip(shapes, norms)):

@@ -74,13 +74,12 @@ class ReliableConvBboxHead(nn.Module):
         shapes = [(m.conv.in_channels, m.conv.out_channels) for m in trunk]
         norms = [m.norm for m in trunk]
         if not all(m.act_fused for m in trunk) or \
-                not fused_mlp.stack1d_supported(backend_for(feats), feats, shapes, norms, which=fused_mlp.PRED):
+                not fused_mlp.stack1d_supported(backend_for(feats), feats, shapes, norms):
             return None
         x = fused_mlp.stack1d(feats, [m.conv for m in trunk], norms)
 
-        def out_conv(conv):     # one bias-carrying layer of the same kernel each (OUT bit of NESIE_STACK1D)
-            if fused_mlp.stack1d_supported(backend_for(x), x, [(conv.in_channels, conv.out_channels)], [None],
-                                           which=fused_mlp.PRED_OUT):
+        def out_conv(conv):     # one bias-carrying layer of the same kernel each
+            if fused_mlp.stack1d_supported(backend_for(x), x, [(conv.in_channels, conv.out_channels)], [None]):
                 return fused_mlp.stack1d(x, [conv], [None])
             return conv(x)
         return out_conv(self.conv_cls), torch.cat((out_conv(self.conv_bbox), out_conv(self.conv_heading)), dim=1)

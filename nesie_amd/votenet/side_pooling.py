@@ -307,7 +307,7 @@ def fused_mini_pointnets(nets, c0, c0_stats):
     # cost two zero-filled slice gradients and two additions)
     w_g, w_l = w.split(half, dim=2)
     gx = g.reshape(B * S, half, g.shape[-1])
-    if not evaluating and fused_mlp.stack1d_supported(backend, gx, [(half, H2)], [None], S, which=fused_mlp.HEADS):
+    if not evaluating and fused_mlp.stack1d_supported(backend, gx, [(half, H2)], [None], S):
         # ... as ONE bias-carrying layer of the layer kernel over the K proposals (weight group =
         # net): W_g g + (W_g b3 + W_l b3); the bias is two tiny products of parameters
         bias = torch.matmul(w, torch.cat([b3, b3], 1).unsqueeze(-1)).reshape(-1)          # (S * H2)
@@ -398,7 +398,7 @@ def _heads_as_stack(heads, x, steps, weights, biases):
             i += 1
     shapes = [(c[0].in_channels, c[0].out_channels) for c in convs]
     if not fused_mlp.stack1d_supported(backend_for(x), x.reshape(B * S, cin, P), shapes,
-                                       [None if n is None else n[0] for n in norms], S, which=fused_mlp.HEADS):
+                                       [None if n is None else n[0] for n in norms], S):
         return None
     bn_groups = [g for n in norms if n is not None for g in ([l.weight for l in n], [l.bias for l in n])]
     stacked = iter(fused_mlp.stack_groups(bn_groups)) if bn_groups else iter(())

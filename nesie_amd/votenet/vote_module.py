@@ -73,7 +73,7 @@ class VoteModule(nn.Module):
         norms = [m.norm for m in self.vote_conv] + [None]
         shapes = [(c.in_channels, c.out_channels) for c in convs]
         if all(m.act_fused for m in self.vote_conv) and \
-                fused_mlp.stack1d_supported(backend_for(seed_feats), seed_feats, shapes, norms, which=fused_mlp.VOTE):
+                fused_mlp.stack1d_supported(backend_for(seed_feats), seed_feats, shapes, norms):
             return fused_mlp.stack1d(seed_feats, convs, norms)
         return self.conv_out(self.vote_conv(seed_feats))
 

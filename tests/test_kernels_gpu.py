@@ -370,9 +370,9 @@ def test_blend_conv_matches_oracle(oracle_kernels, hip_device, k, segs, g, h):
 def test_staged_blend_backward_is_reproducible_and_equals_the_atomic_form(hip_device, k, segs, g, h, hot):
     """nesie_blend_conv_backward_staged with most taps on a few seeds (`hot`): a seed then collects
     rows from hundreds of 16-query groups, other seeds none at all.  Three evaluations: same bits;
-    against a float64 scatter: rounding only; against the atomic form (NESIE_BLEND_STAGED=0's code
-    path, zero-filled table): summation order only; rows of seeds without taps are written as zeros
-    into a table that arrives full of NaN."""
+    against a float64 scatter: rounding only; against the atomic form (the path that
+    set_deterministic(False) selects, zero-filled table): summation order only; rows of seeds
+    without taps are written as zeros into a table that arrives full of NaN."""
     hip = kernels.backend_for(torch.empty(1, device=hip_device))
     prev = hip.set_deterministic(True)
     try:

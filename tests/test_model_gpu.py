@@ -503,7 +503,7 @@ def test_stream_first_layer_equals_the_gemm_path(hip_device):
 
 
 def test_folded_norm_backward_matches_the_separate_apply_pass(hip_device):
-    """NESIE_FOLD_NORM_BWD on vs off on the reduced model, one training step from the same state:
+    """fused_mlp.FOLD_NORM_BWD on vs off on the reduced model, one training step from the same state:
     the norm backward applied inside its consumer -- the weight gradient (SA stacks, 1-D chains,
     MiniPointNet norm 1 with the row-bias gradient) or the blend backward (MiniPointNet norm 0,
     inside the one autograd node fused_mlp.BlendMiniHeadFn) -- gives the gradients of the separate

@@ -553,16 +553,7 @@ static int fps_launch(int b, int n, int m, const float *xyz, float *temp, int *i
       ((uintptr_t)workspace & 15) == 0) {
     float4 *wp = (float4 *)workspace;
     unsigned *wo = (unsigned *)((char *)workspace + (size_t)b * n * 16);
-    static const int nw = [] {
-      const char *e = getenv("NESIE_FPS_WAVES");
-      return e ? atoi(e) : 4;
-    }();
-    if (nw == 16)
-      hipLaunchKernelGGL(fps_pruned_kernel<16>, grid, dim3(1024), 0, s, n, m, xyz, temp, idx, wp, wo);
-    else if (nw == 8)
-      hipLaunchKernelGGL(fps_pruned_kernel<8>, grid, dim3(512), 0, s, n, m, xyz, temp, idx, wp, wo);
-    else
-      hipLaunchKernelGGL(fps_pruned_kernel<4>, grid, dim3(256), 0, s, n, m, xyz, temp, idx, wp, wo);
+    hipLaunchKernelGGL(fps_pruned_kernel<16>, grid, dim3(1024), 0, s, n, m, xyz, temp, idx, wp, wo);
     return check_launch(W);
   }
   if (n <= 64) REG(64, 1);

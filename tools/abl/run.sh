@@ -8,5 +8,5 @@ for a in 0 1 2; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -std=c++17 -DABL=$a -I$R/nesie_amd/csrc -c $R/tools/abl/fps_abl.hip -o /tmp/abl$a/fps.o
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/abl$a/libnesie_hip.so /tmp/abl$a/*.o
   echo "ABL=$a"
-  NESIE_LIB=/tmp/abl$a/libnesie_hip.so NESIE_FPS_WAVES=16 B=8 python $R/tools/opbench.py 2>&1 | grep -E "fps 40000"
+  NESIE_LIB=/tmp/abl$a/libnesie_hip.so B=8 python $R/tools/opbench.py 2>&1 | grep -E "fps 40000"
 done

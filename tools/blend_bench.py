@@ -45,4 +45,4 @@ e.record()
 torch.cuda.synchronize()
 gb = (2 * dy.numel() * 4) / 1e9
 print(f'{which}: {s.elapsed_time(e) / 10 * 1e3:.1f} us per call (rows + slot index + gather + d_wx sum), '
-      f'{gb:.2f} GB of (dA, Z) read; NESIE_BLEND_ABL={os.environ.get("NESIE_BLEND_ABL", "0")}', flush=True)
+      f'{gb:.2f} GB of (dA, Z) read', flush=True)

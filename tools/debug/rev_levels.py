@@ -1,5 +1,5 @@
 """Debug aid: checksums of the backbone's per-level outputs and head predictions of one training-mode
-forward at B scenes (compare two runs with different NESIE_PW_REV_* settings)."""
+forward at B scenes (compare two runs with different NESIE_PW_REV_MB settings)."""
 import sys
 sys.path.insert(0, '.')
 import torch
