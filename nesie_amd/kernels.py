@@ -22,16 +22,16 @@ from . import _lib
 _injected = None
 
 
-def _ptr(t):
-    return t.data_ptr()
+def _no_cpu_path(device):
+    return RuntimeError(
+        "nesie_amd kernels need HIP device tensors (got device "
+        f"{device}); there is no CPU path in the product")
 
 
 def _check(*tensors):
     for t in tensors:
         if not t.is_cuda:
-            raise RuntimeError(
-                "nesie_amd kernels need HIP device tensors (got device "
-                f"{t.device}); there is no CPU path in the product")
+            raise _no_cpu_path(t.device)
         if not t.is_contiguous():
             raise RuntimeError("nesie_amd kernels need contiguous tensors")
 
@@ -48,46 +48,41 @@ def _i32(*ts):
             raise TypeError(f"expected int32, got {t.dtype}")
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+def _launch(name, on, *args):
+    """Call the entry point ``name`` on the device and current stream of ``on`` (a tensor, or the
+    torch.device itself for a call without tensors); the stream is appended as the last argument.
+    A tensor is passed as its address, None as a null pointer, a bool as 0 / 1.  The call is
+    checked against the header's prototype first: the argument count, and no tensor or None
+    outside a pointer slot, no float inside one."""
+    argtypes = _lib.SIGNATURES[name][1]
+    if len(args) + 1 != len(argtypes):
+        raise TypeError(f"{name}: {len(args)} arguments and the stream given, "
+                        f"the header declares {len(argtypes)}")
+    out = []
+    for slot, (a, ctype) in enumerate(zip(args, argtypes)):
+        if a is None or isinstance(a, torch.Tensor):
+            if ctype is not ctypes.c_void_p:
+                raise TypeError(f"{name}: argument {slot} is a {ctype.__name__} in the header, got "
+                                + ("None" if a is None else "a tensor"))
+            a = 0 if a is None else a.data_ptr()
+        elif ctype is ctypes.c_void_p and isinstance(a, float):
+            raise TypeError(f"{name}: argument {slot} is a pointer in the header, got a float")
+        elif isinstance(a, bool):
+            a = int(a)
+        out.append(a)
+    device = on.device if isinstance(on, torch.Tensor) else on
+    if device.type != "cuda":
+        raise _no_cpu_path(device)
+    with torch.cuda.device(device):
+        _lib.call(name, *out, torch.cuda.current_stream(device).cuda_stream)
 
 
-class _BNPoolMixin:
-    def bn_relu_maxpool_forward(self, x, gamma, beta, running_mean, running_var, momentum, eps,
-                                pooled, argmax, save_mean, save_invstd, fwd_coef):
-        """x (B, C, M, ns) -> pooled (B, C, M) fp32, argmax (B, C, M) uint8."""
-        _check(x, pooled, argmax, save_mean, save_invstd, fwd_coef); _f32(x, pooled)
-        b, c, m, ns = x.shape
-        assert tuple(pooled.shape) == (b, c, m) and argmax.dtype == torch.uint8
-        with torch.cuda.device(x.device):
-            ws, need = _bn_pool_ws(x)
-            opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-            _lib.call("nesie_bn_relu_maxpool_forward", b, c, m, ns, _ptr(x), opt(gamma),
-                      opt(beta), opt(running_mean), opt(running_var), float(momentum),
-                      float(eps), _ptr(pooled), _ptr(argmax), _ptr(save_mean),
-                      _ptr(save_invstd), _ptr(fwd_coef), _ptr(ws), need, _stream(x))
-
-    def bn_relu_maxpool_backward(self, grad_pooled, argmax, x, pooled, gamma, save_invstd,
-                                 fwd_coef, dx, dgamma, dbeta):
-        _check(grad_pooled, argmax, x, pooled, dx); _f32(grad_pooled, x, pooled, dx)
-        b, c, m, ns = x.shape
-        assert tuple(grad_pooled.shape) == (b, c, m) and dx.shape == x.shape
-        with torch.cuda.device(x.device):
-            ws, need = _bn_pool_ws(x)
-            opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-            _lib.call("nesie_bn_relu_maxpool_backward", b, c, m, ns, _ptr(grad_pooled),
-                      _ptr(argmax), _ptr(x), _ptr(pooled), opt(gamma), opt(save_invstd),
-                      _ptr(fwd_coef), _ptr(dx), opt(dgamma), opt(dbeta), _ptr(ws), need,
-                      _stream(x))
+def _workspace(need, device):
+    """``need`` bytes of kernel scratch from torch's caching allocator (never an empty tensor)."""
+    return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
 
 
-def _bn_pool_ws(x):
-    b, c, m, ns = x.shape
-    need = _lib.load().nesie_bn_workspace_bytes(b, c, m * ns)
-    return torch.empty(max(need, 16), dtype=torch.uint8, device=x.device), need
-
-
-class HipKernels(_BNPoolMixin):
+class HipKernels:
     """libnesie_hip.so, asynchronous on torch's current HIP stream."""
 
     name = "hip"
@@ -130,6 +125,13 @@ class HipKernels(_BNPoolMixin):
         finally:
             _lib.call("nesie_set_cu_count", before)
 
+    @staticmethod
+    def _stream_state(device):
+        """(current stream of ``device``, whether a graph capture is recording it)."""
+        with torch.cuda.device(device):   # is_current_stream_capturing() reads the current device
+            return (torch.cuda.current_stream(device).cuda_stream,
+                    torch.cuda.is_current_stream_capturing())
+
     @classmethod
     def _index_for(cls, xyz, b, n):
         hit = cls._spatial_index.get(xyz.device)
@@ -141,8 +143,7 @@ class HipKernels(_BNPoolMixin):
         # trust it (and vice versa)
         same = (ref.data_ptr() == xyz.data_ptr() and ref._version == version
                 and xyz._version == version and shape == (b, n) and ref.dtype == xyz.dtype
-                and stream == _stream(xyz)
-                and capturing == torch.cuda.is_current_stream_capturing())
+                and (stream, capturing) == cls._stream_state(xyz.device))
         return ws if same else None
 
     def furthest_point_sampling_wrapper(self, b, n, m, xyz, temp, idx):
@@ -150,74 +151,59 @@ class HipKernels(_BNPoolMixin):
         assert xyz.numel() == b * n * 3 and temp.numel() == b * n and idx.numel() == b * m
         lib = _lib.load()
         need = lib.nesie_fps_workspace_bytes(b, n)
-        with torch.cuda.device(xyz.device):
-            if need:
-                # scratch for the bucket-pruned kernel, from torch's caching allocator
-                ws = torch.empty(need, dtype=torch.uint8, device=xyz.device)
-                _lib.call("nesie_furthest_point_sampling_ws", b, n, m, _ptr(xyz),
-                          _ptr(temp), _ptr(idx), _ptr(ws), need, _stream(xyz))
-                if HipKernels._index_scope_depth > 0 and lib.nesie_fps_leaves_index(b, n):
-                    HipKernels._spatial_index[xyz.device] = (
-                        xyz, xyz._version, (b, n), ws, _stream(xyz),
-                        torch.cuda.is_current_stream_capturing())
-            else:
-                _lib.call("nesie_furthest_point_sampling_wrapper", b, n, m, _ptr(xyz),
-                          _ptr(temp), _ptr(idx), _stream(xyz))
+        if need:
+            # scratch for the bucket-pruned kernel, from torch's caching allocator
+            ws = torch.empty(need, dtype=torch.uint8, device=xyz.device)
+            _launch("nesie_furthest_point_sampling_ws", xyz, b, n, m, xyz, temp, idx, ws, need)
+            if HipKernels._index_scope_depth > 0 and lib.nesie_fps_leaves_index(b, n):
+                HipKernels._spatial_index[xyz.device] = (
+                    xyz, xyz._version, (b, n), ws, *self._stream_state(xyz.device))
+        else:
+            _launch("nesie_furthest_point_sampling_wrapper", xyz, b, n, m, xyz, temp, idx)
 
     def furthest_point_sampling_with_dist_wrapper(self, b, n, m, dist, temp, idx):
         _check(dist, temp, idx); _f32(dist, temp); _i32(idx)
         assert dist.numel() == b * n * n and temp.numel() == b * n and idx.numel() == b * m
-        with torch.cuda.device(dist.device):
-            _lib.call("nesie_furthest_point_sampling_with_dist_wrapper", b, n, m,
-                      _ptr(dist), _ptr(temp), _ptr(idx), _stream(dist))
+        _launch("nesie_furthest_point_sampling_with_dist_wrapper", dist, b, n, m, dist, temp, idx)
 
     def ball_query_wrapper(self, b, n, m, min_radius, max_radius, nsample, new_xyz, xyz,
                            idx):
         _check(new_xyz, xyz, idx); _f32(new_xyz, xyz); _i32(idx)
         assert new_xyz.numel() == b * m * 3 and xyz.numel() == b * n * 3
         assert idx.numel() == b * m * nsample
-        with torch.cuda.device(xyz.device):
-            ws = self._index_for(xyz, b, n) if nsample <= 64 else None
-            if ws is not None:  # same results, only the buckets within max_radius are visited
-                _lib.call("nesie_ball_query_indexed", b, n, m, float(min_radius),
-                          float(max_radius), nsample, _ptr(new_xyz), _ptr(ws), ws.numel(),
-                          _ptr(idx), _stream(xyz))
-                return
-            _lib.call("nesie_ball_query_wrapper", b, n, m, float(min_radius),
-                      float(max_radius), nsample, _ptr(new_xyz), _ptr(xyz), _ptr(idx),
-                      _stream(xyz))
+        ws = self._index_for(xyz, b, n) if nsample <= 64 else None
+        if ws is not None:  # same results, only the buckets within max_radius are visited
+            _launch("nesie_ball_query_indexed", xyz, b, n, m, float(min_radius), float(max_radius),
+                    nsample, new_xyz, ws, ws.numel(), idx)
+            return
+        _launch("nesie_ball_query_wrapper", xyz, b, n, m, float(min_radius), float(max_radius),
+                nsample, new_xyz, xyz, idx)
 
     def group_points_forward(self, b, c, n, npoints, nsample, points, idx, out):
         _check(points, idx, out); _f32(points, out); _i32(idx)
         assert points.numel() == b * c * n and idx.numel() == b * npoints * nsample
         assert out.numel() == b * c * npoints * nsample
-        with torch.cuda.device(points.device):
-            _lib.call("nesie_group_points_forward", b, c, n, npoints, nsample,
-                      _ptr(points), _ptr(idx), _ptr(out), _stream(points))
+        _launch("nesie_group_points_forward", points, b, c, n, npoints, nsample, points, idx, out)
 
     def group_points_backward(self, b, c, n, npoints, nsample, grad_out, idx, grad_points):
         _check(grad_out, idx, grad_points); _f32(grad_out, grad_points); _i32(idx)
         assert grad_out.numel() == b * c * npoints * nsample
         assert idx.numel() == b * npoints * nsample and grad_points.numel() == b * c * n
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_group_points_backward", b, c, n, npoints, nsample,
-                      _ptr(grad_out), _ptr(idx), _ptr(grad_points), _stream(grad_out))
+        _launch("nesie_group_points_backward", grad_out, b, c, n, npoints, nsample, grad_out, idx,
+                grad_points)
 
     def gather_points_wrapper(self, b, c, n, npoints, points, idx, out):
         _check(points, idx, out); _f32(points, out); _i32(idx)
         assert points.numel() == b * c * n and idx.numel() == b * npoints
         assert out.numel() == b * c * npoints
-        with torch.cuda.device(points.device):
-            _lib.call("nesie_gather_points_wrapper", b, c, n, npoints, _ptr(points),
-                      _ptr(idx), _ptr(out), _stream(points))
+        _launch("nesie_gather_points_wrapper", points, b, c, n, npoints, points, idx, out)
 
     def gather_points_grad_wrapper(self, b, c, n, npoints, grad_out, idx, grad_points):
         _check(grad_out, idx, grad_points); _f32(grad_out, grad_points); _i32(idx)
         assert grad_out.numel() == b * c * npoints and idx.numel() == b * npoints
         assert grad_points.numel() == b * c * n
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_gather_points_grad_wrapper", b, c, n, npoints,
-                      _ptr(grad_out), _ptr(idx), _ptr(grad_points), _stream(grad_out))
+        _launch("nesie_gather_points_grad_wrapper", grad_out, b, c, n, npoints, grad_out, idx,
+                grad_points)
 
     def query_and_group_forward(self, xyz, centres, features, idx, radius, out):
         """out (B, 3+C, M, ns) = cat[(xyz[idx] - centre) / radius, features[idx]]."""
@@ -229,10 +215,8 @@ class HipKernels(_BNPoolMixin):
             _check(features); _f32(features)
             assert tuple(features.shape) == (b, c, n)
         assert tuple(out.shape) == (b, 3 + c, m, ns) and tuple(centres.shape) == (b, m, 3)
-        with torch.cuda.device(xyz.device):
-            _lib.call("nesie_query_and_group_forward", b, c, n, m, ns, _ptr(xyz), _ptr(centres),
-                      0 if features is None else _ptr(features), _ptr(idx), float(radius),
-                      _ptr(out), _stream(xyz))
+        _launch("nesie_query_and_group_forward", xyz, b, c, n, m, ns, xyz, centres, features, idx,
+                float(radius), out)
 
     def query_and_group_backward(self, grad_out, idx, grad_features):
         """grad_features (B,C,N) zeroed += channels 3.. of grad_out (B, 3+C, M, ns)."""
@@ -240,9 +224,8 @@ class HipKernels(_BNPoolMixin):
         b, c, n = grad_features.shape
         m, ns = idx.shape[1], idx.shape[2]
         assert tuple(grad_out.shape) == (b, 3 + c, m, ns)
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_query_and_group_backward", b, c, n, m, ns, _ptr(grad_out), _ptr(idx),
-                      _ptr(grad_features), _stream(grad_out))
+        _launch("nesie_query_and_group_backward", grad_out, b, c, n, m, ns, grad_out, idx,
+                grad_features)
 
     def three_interpolate_grad_csr(self, grad_out, weight, order, sources, grad_points):
         """grad_points (B,C,m) = scatter of weight * grad_out (B,C,n) through (order, sources) =
@@ -254,10 +237,8 @@ class HipKernels(_BNPoolMixin):
         m = grad_points.shape[2]
         assert grad_out.is_cuda and grad_out.stride(2) == 1 and grad_out.stride(1) == n
         assert weight.numel() == b * n * 3 and tuple(order.shape) == (b, n * 3)
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_three_interpolate_grad_csr", b, c, n, m, _ptr(grad_out),
-                      grad_out.stride(0) if b > 1 else c * n, _ptr(weight), _ptr(order), _ptr(sources),
-                      _ptr(grad_points), _stream(grad_out))
+        _launch("nesie_three_interpolate_grad_csr", grad_out, b, c, n, m, grad_out,
+                grad_out.stride(0) if b > 1 else c * n, weight, order, sources, grad_points)
 
     def inverted_index(self, idx, n):
         """idx (B, M, ns) int32 in [0, n) -> order, sources (B, M*ns) int32: the grouped columns
@@ -268,9 +249,7 @@ class HipKernels(_BNPoolMixin):
         order = torch.empty(b, e, dtype=torch.int32, device=idx.device)
         sources = torch.empty(b, e, dtype=torch.int32, device=idx.device)
         scratch = torch.empty(b, e, dtype=torch.int32, device=idx.device)
-        with torch.cuda.device(idx.device):
-            _lib.call("nesie_inverted_index", b, n, e, _ptr(idx), _ptr(order), _ptr(sources),
-                      _ptr(scratch), _stream(idx))
+        _launch("nesie_inverted_index", idx, b, n, e, idx, order, sources, scratch)
         return order, sources
 
     def vote_finish_forward(self, raw, seed_points, seed_feats, normalise):
@@ -280,9 +259,8 @@ class HipKernels(_BNPoolMixin):
         assert tuple(raw.shape) == (b, 3 + c, n) and tuple(seed_points.shape) == (b, n, 3)
         vp, vf = torch.empty_like(seed_points), torch.empty_like(seed_feats)
         inv = torch.empty(b, n, dtype=torch.float32, device=raw.device)
-        with torch.cuda.device(raw.device):
-            _lib.call("nesie_vote_finish_forward", b, c, n, int(bool(normalise)), _ptr(raw), _ptr(seed_points),
-                      _ptr(seed_feats), _ptr(vp), _ptr(vf), _ptr(inv), _stream(raw))
+        _launch("nesie_vote_finish_forward", raw, b, c, n, bool(normalise), raw, seed_points,
+                seed_feats, vp, vf, inv)
         return vp, vf, inv
 
     def vote_finish_backward(self, g_feats, g_points, vote_feats, inv_norm, normalise):
@@ -294,10 +272,8 @@ class HipKernels(_BNPoolMixin):
                 _check(t); _f32(t)
                 assert tuple(t.shape) == shape
         d_raw = torch.empty(b, 3 + c, n, dtype=torch.float32, device=vote_feats.device)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(vote_feats.device):
-            _lib.call("nesie_vote_finish_backward", b, c, n, int(bool(normalise)), opt(g_feats), opt(g_points),
-                      _ptr(vote_feats), _ptr(inv_norm), _ptr(d_raw), _stream(vote_feats))
+        _launch("nesie_vote_finish_backward", vote_feats, b, c, n, bool(normalise), g_feats,
+                g_points, vote_feats, inv_norm, d_raw)
         return d_raw
 
     def gather_rows3(self, xyz, sample):
@@ -306,8 +282,7 @@ class HipKernels(_BNPoolMixin):
         b, n = xyz.shape[:2]
         m = sample.shape[1]
         out = torch.empty(b, m, 3, dtype=torch.float32, device=xyz.device)
-        with torch.cuda.device(xyz.device):
-            _lib.call("nesie_gather_rows3", b, n, m, _ptr(xyz), _ptr(sample), _ptr(out), _stream(xyz))
+        _launch("nesie_gather_rows3", xyz, b, n, m, xyz, sample, out)
         return out
 
     def query_and_group_backward_xyz(self, grad_out, radius, order, sources, sample, d_centres, n):
@@ -321,10 +296,8 @@ class HipKernels(_BNPoolMixin):
             _check(d_centres); _f32(d_centres)
             assert tuple(d_centres.shape) == (b, m, 3)
         d_xyz = torch.empty(b, n, 3, dtype=torch.float32, device=grad_out.device)
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_query_and_group_backward_xyz", b, c3 - 3, n, m, ns, float(radius),
-                      _ptr(grad_out), _ptr(order), _ptr(sources), _ptr(sample),
-                      0 if d_centres is None else _ptr(d_centres), _ptr(d_xyz), _stream(grad_out))
+        _launch("nesie_query_and_group_backward_xyz", grad_out, b, c3 - 3, n, m, ns, float(radius),
+                grad_out, order, sources, sample, d_centres, d_xyz)
         return d_xyz
 
     def query_and_group_backward_csr(self, grad_out, idx_shape, order, offsets, grad_features):
@@ -336,9 +309,8 @@ class HipKernels(_BNPoolMixin):
         m, ns = idx_shape[1], idx_shape[2]
         assert tuple(grad_out.shape) == (b, 3 + c, m, ns)
         assert tuple(order.shape) == (b, m * ns) and tuple(offsets.shape) == (b, m * ns)
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_query_and_group_backward_csr", b, c, n, m, ns, _ptr(grad_out),
-                      _ptr(order), _ptr(offsets), _ptr(grad_features), _stream(grad_out))
+        _launch("nesie_query_and_group_backward_csr", grad_out, b, c, n, m, ns, grad_out, order,
+                offsets, grad_features)
 
     def group_points_backward_csr(self, grad_out, order, sources, grad_points):
         """grad_points (B,C,N) = scatter of grad_out (B,C,M,ns) through (order, sources) =
@@ -348,57 +320,46 @@ class HipKernels(_BNPoolMixin):
         b, c, n = grad_points.shape
         m, ns = grad_out.shape[2], grad_out.shape[3]
         assert grad_out.shape[:2] == (b, c) and tuple(order.shape) == (b, m * ns) == tuple(sources.shape)
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_group_points_backward_csr", b, c, n, m, ns, _ptr(grad_out), _ptr(order),
-                      _ptr(sources), _ptr(grad_points), _stream(grad_out))
+        _launch("nesie_group_points_backward_csr", grad_out, b, c, n, m, ns, grad_out, order,
+                sources, grad_points)
 
     def three_nn_wrapper(self, b, n, m, unknown, known, dist2, idx):
         _check(unknown, known, dist2, idx); _f32(unknown, known, dist2); _i32(idx)
         assert unknown.numel() == b * n * 3 and known.numel() == b * m * 3
         assert dist2.numel() == b * n * 3 and idx.numel() == b * n * 3
-        with torch.cuda.device(unknown.device):
-            _lib.call("nesie_three_nn_wrapper", b, n, m, _ptr(unknown), _ptr(known),
-                      _ptr(dist2), _ptr(idx), _stream(unknown))
+        _launch("nesie_three_nn_wrapper", unknown, b, n, m, unknown, known, dist2, idx)
 
     def three_interpolate_wrapper(self, b, c, m, n, points, idx, weight, out):
         _check(points, idx, weight, out); _f32(points, weight, out); _i32(idx)
         assert points.numel() == b * c * m and idx.numel() == b * n * 3
         assert weight.numel() == b * n * 3 and out.numel() == b * c * n
-        with torch.cuda.device(points.device):
-            _lib.call("nesie_three_interpolate_wrapper", b, c, m, n, _ptr(points),
-                      _ptr(idx), _ptr(weight), _ptr(out), _stream(points))
+        _launch("nesie_three_interpolate_wrapper", points, b, c, m, n, points, idx, weight, out)
 
     def side_decode_forward(self, reg, agg, scale, sign, probs, surface, bbox):
         _check(reg, agg, scale, sign, probs, surface, bbox); _f32(reg, agg, probs, surface, bbox)
         b, cch, k = reg.shape
         bins = (cch - 2) // 6
         assert tuple(probs.shape) == (b, 6, bins, k) and tuple(bbox.shape) == (b, k, 7)
-        with torch.cuda.device(reg.device):
-            _lib.call("nesie_side_decode_forward", b, k, bins, _ptr(reg), _ptr(agg), _ptr(scale),
-                      _ptr(sign), _ptr(probs), _ptr(surface), _ptr(bbox), _stream(reg))
+        _launch("nesie_side_decode_forward", reg, b, k, bins, reg, agg, scale, sign, probs, surface,
+                bbox)
 
     def side_decode_backward(self, reg, probs, scale, sign, d_surface, d_bbox, d_reg, d_agg):
         _check(reg, probs, scale, sign, d_reg, d_agg)
         b, cch, k = reg.shape
         bins = (cch - 2) // 6
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
         for t in (d_surface, d_bbox):
             if t is not None:
                 _check(t); _f32(t)
-        with torch.cuda.device(reg.device):
-            _lib.call("nesie_side_decode_backward", b, k, bins, _ptr(reg), _ptr(probs),
-                      _ptr(scale), _ptr(sign), opt(d_surface), opt(d_bbox), _ptr(d_reg),
-                      _ptr(d_agg), _stream(reg))
+        _launch("nesie_side_decode_backward", reg, b, k, bins, reg, probs, scale, sign, d_surface,
+                d_bbox, d_reg, d_agg)
 
     def bn_eval_coef(self, gamma, beta, running_mean, running_var, eps, coef):
         """coef (C,4) <- (gamma / sqrt(var + eps), beta - mean * scale, 0, 0); one launch."""
         _check(running_mean, running_var, coef); _f32(running_mean, running_var, coef)
         c = running_mean.numel()
         assert tuple(coef.shape) == (c, 4) and coef.is_contiguous()
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(coef.device):
-            _lib.call("nesie_bn_eval_coef", c, opt(gamma), opt(beta), _ptr(running_mean),
-                      _ptr(running_var), float(eps), _ptr(coef), _stream(coef))
+        _launch("nesie_bn_eval_coef", coef, c, gamma, beta, running_mean, running_var, float(eps),
+                coef)
 
     def affine_relu_forward(self, x, coef, relu, y, row_bias=None):
         """Evaluation-mode norm: y = relu?(coef[c,0] * (x + row_bias) + coef[c,1]); x, y (B,C,*)."""
@@ -407,9 +368,7 @@ class HipKernels(_BNPoolMixin):
         p = x.numel() // (b * c) if b * c else 0
         assert tuple(coef.shape) == (c, 4) and y.shape == x.shape
         group = _row_bias_group(x, row_bias)
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_affine_relu_forward", b, c, p, _ptr(x), _ptr(coef), int(bool(relu)),
-                      0 if row_bias is None else _ptr(row_bias), group, _ptr(y), _stream(x))
+        _launch("nesie_affine_relu_forward", x, b, c, p, x, coef, bool(relu), row_bias, group, y)
 
     def affine_relu_maxpool_forward(self, x, coef, pooled, argmax):
         """x (B,C,M,ns) -> pooled (B,C,M) = max_ns relu(coef[c,0] * x + coef[c,1]), argmax u8."""
@@ -417,9 +376,7 @@ class HipKernels(_BNPoolMixin):
         b, c, m, ns = x.shape
         assert tuple(coef.shape) == (c, 4) and tuple(pooled.shape) == (b, c, m)
         assert argmax.dtype == torch.uint8 and tuple(argmax.shape) == (b, c, m)
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_affine_relu_maxpool_forward", b, c, m, ns, _ptr(x), _ptr(coef),
-                      _ptr(pooled), _ptr(argmax), _stream(x))
+        _launch("nesie_affine_relu_maxpool_forward", x, b, c, m, ns, x, coef, pooled, argmax)
 
     def mlp_stream_forward(self, x, w, y, stat_partial=None, in_coef=None, in_relu=False):
         """y[b] = W . act(x[b]) on the matrix cores, streaming form (Cin <= 64, Cout <= 128):
@@ -437,11 +394,8 @@ class HipKernels(_BNPoolMixin):
         if stat_partial is not None:
             _check(stat_partial); _f32(stat_partial)
             assert tuple(stat_partial.shape) == (self.mlp_stream_parts(b, p), cout, 2)
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_mlp_layer_forward_stream", b, cin, cout, p, _ptr(x), cin * p,
-                      _ptr(w), 0 if in_coef is None else _ptr(in_coef), int(bool(in_relu)),
-                      0 if y is None else _ptr(y), 0 if stat_partial is None else _ptr(stat_partial),
-                      _stream(x))
+        _launch("nesie_mlp_layer_forward_stream", x, b, cin, cout, p, x, cin * p, w, in_coef,
+                bool(in_relu), y, stat_partial)
 
     @staticmethod
     def mlp_stream_parts(b, p):
@@ -457,19 +411,15 @@ class HipKernels(_BNPoolMixin):
         if valid is not None:
             _check(valid)
             assert valid.dtype == torch.uint8 and tuple(valid.shape) == (b, k)
-        with torch.cuda.device(boxes.device):
-            _lib.call("nesie_aligned_3d_nms", b, k, _ptr(boxes), _ptr(scores), _ptr(classes),
-                      0 if valid is None else _ptr(valid), float(thr), _ptr(picks), _ptr(count),
-                      _stream(boxes))
+        _launch("nesie_aligned_3d_nms", boxes, b, k, boxes, scores, classes, valid, float(thr),
+                picks, count)
 
     def points_in_boxes_count(self, boxes, pts, counts):
         """boxes (B,T,7) LiDAR frame, pts (B,M,3) -> counts (B,T) i32."""
         _check(boxes, pts, counts); _f32(boxes, pts); _i32(counts)
         b, t, _ = boxes.shape
         assert pts.shape[0] == b and pts.shape[2] == 3 and tuple(counts.shape) == (b, t)
-        with torch.cuda.device(boxes.device):
-            _lib.call("nesie_points_in_boxes_count", b, t, pts.shape[1], _ptr(boxes), _ptr(pts),
-                      _ptr(counts), _stream(boxes))
+        _launch("nesie_points_in_boxes_count", boxes, b, t, pts.shape[1], boxes, pts, counts)
 
     def boxes_overlap_bev(self, boxes_a, boxes_b, ans_overlap):
         """(N,5), (M,5) rotated BEV rectangles (x1,y1,x2,y2,angle) -> overlap areas (N,M)."""
@@ -477,9 +427,7 @@ class HipKernels(_BNPoolMixin):
         n, m = boxes_a.shape[0], boxes_b.shape[0]
         assert boxes_a.shape[1] == 5 and boxes_b.shape[1] == 5
         assert tuple(ans_overlap.shape) == (n, m)
-        with torch.cuda.device(boxes_a.device):
-            _lib.call("nesie_boxes_overlap_bev", n, _ptr(boxes_a), m, _ptr(boxes_b),
-                      _ptr(ans_overlap), _stream(boxes_a))
+        _launch("nesie_boxes_overlap_bev", boxes_a, n, boxes_a, m, boxes_b, ans_overlap)
 
     def bev_nms(self, boxes, scores, valid, offsets, max_seg, thr, rotated, keep, count, ws):
         """(n,5) (x1,y1,x2,y2,ry), scores (n), valid (n) u8 or None, offsets (S+1) i32 ->
@@ -490,11 +438,8 @@ class HipKernels(_BNPoolMixin):
         if valid is not None:
             _check(valid)
             assert valid.dtype == torch.uint8 and valid.numel() == n
-        with torch.cuda.device(boxes.device):
-            _lib.call("nesie_bev_nms", n, s, int(max_seg), _ptr(boxes), _ptr(scores),
-                      0 if valid is None else _ptr(valid), _ptr(offsets), float(thr),
-                      1 if rotated else 0, _ptr(keep), _ptr(count), _ptr(ws),
-                      ws.numel() * ws.element_size(), _stream(boxes))
+        _launch("nesie_bev_nms", boxes, n, s, int(max_seg), boxes, scores, valid, offsets,
+                float(thr), 1 if rotated else 0, keep, count, ws, ws.numel() * ws.element_size())
 
     def scene_assemble(self, pool, height, choices, xform, out):
         """pool (R,3), height (R), choices (B,n) i32 rows of the pool, xform (B,20) -> out (B,n,4)."""
@@ -502,9 +447,8 @@ class HipKernels(_BNPoolMixin):
         b, n = choices.shape
         assert pool.dim() == 2 and pool.shape[1] == 3 and height.numel() == pool.shape[0]
         assert tuple(xform.shape) == (b, 20) and tuple(out.shape) == (b, n, 4)
-        with torch.cuda.device(pool.device):
-            _lib.call("nesie_scene_assemble", b, n, pool.shape[0], _ptr(pool), _ptr(height),
-                      _ptr(choices), _ptr(xform), _ptr(out), _stream(pool))
+        _launch("nesie_scene_assemble", pool, b, n, pool.shape[0], pool, height, choices, xform,
+                out)
 
     def grid_taps(self, centre, size, heading, mult, plane, known):
         """-> idx (B,K*gp,3) int32, weight, rel (B,K*gp,3) for the gp grid points per proposal."""
@@ -517,10 +461,8 @@ class HipKernels(_BNPoolMixin):
         idx = torch.empty(b, k * gp, 3, dtype=torch.int32, device=centre.device)
         weight = torch.empty(b, k * gp, 3, dtype=torch.float32, device=centre.device)
         rel = torch.empty_like(weight)
-        with torch.cuda.device(centre.device):
-            _lib.call("nesie_grid_taps", b, k, gp, m, _ptr(centre), _ptr(size), _ptr(heading),
-                      _ptr(mult), _ptr(plane), _ptr(known), _ptr(idx), _ptr(weight), _ptr(rel),
-                      _stream(centre))
+        _launch("nesie_grid_taps", centre, b, k, gp, m, centre, size, heading, mult, plane, known,
+                idx, weight, rel)
         return idx, weight, rel
 
     def blend_conv_forward(self, table, seg_off, idx, weight, rel, wx, out, segs, seg_len,
@@ -537,14 +479,11 @@ class HipKernels(_BNPoolMixin):
         if wx is not None:
             _check(rel, wx); _f32(rel, wx)
             assert rel.numel() == b * n * 3 and tuple(wx.shape) == (segs, c, 3)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(table.device):
-            if stat_partial is not None:
-                _check(stat_partial); _f32(stat_partial)
-                assert stat_partial.numel() == segs * c * (b * (n // segs // 64)) * 2
-            _lib.call("nesie_blend_conv_forward", b, c, m, n, _ptr(table), pitch, seg_off,
-                      _ptr(idx), _ptr(weight), opt(rel), opt(wx), _ptr(out), segs, seg_len,
-                      int(out.shape[2]), c_offset, opt(stat_partial), _stream(table))
+        if stat_partial is not None:
+            _check(stat_partial); _f32(stat_partial)
+            assert stat_partial.numel() == segs * c * (b * (n // segs // 64)) * 2
+        _launch("nesie_blend_conv_forward", table, b, c, m, n, table, pitch, seg_off, idx, weight,
+                rel, wx, out, segs, seg_len, int(out.shape[2]), c_offset, stat_partial)
 
     # Deterministic backward -- THE DEFAULT since round 5 (NESIE_DETERMINISTIC=0 or
     # ``set_deterministic(False)`` restores the reference's atomicAdd scatters,
@@ -590,37 +529,32 @@ class HipKernels(_BNPoolMixin):
         if d_wx is not None:
             _check(rel, d_wx); _f32(rel, d_wx)
             assert tuple(d_wx.shape) == (segs, c, 3)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(dy.device):
-            part = None
-            if d_wx is not None:   # one partial per workgroup, summed here
-                runs = _lib.load().nesie_blend_conv_runs(n, segs)
-                part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
-            if bnb is not None:
-                _check(bn_z, bnb); _f32(bn_z, bnb)
-                assert tuple(bn_z.shape) == tuple(dy.shape) and tuple(bnb.shape) == (segs * c, 8)
-            if self.DETERMINISTIC and not self.blend_backward_writes_table(c, n, segs, m):
-                raise RuntimeError(
-                    f'blend_conv_backward: no fixed-order form for c={c}, {n // segs} queries per face, '
-                    f'{m} seeds (needs c in 64..256 step 64, faces of whole 64-query tiles, <= 2047 '
-                    'seeds); HipKernels.set_deterministic(False) selects the atomic scatter')
-            if self.blend_backward_writes_table(c, n, segs, m):
-                assert seg_off == c or segs == 1, 'staged form: one column block per face'
-                need = _lib.load().nesie_blend_conv_backward_workspace_bytes(b, c, n, segs)
-                ws = torch.empty(need, dtype=torch.uint8, device=dy.device)
-                _lib.call("nesie_blend_conv_backward_staged", b, c, m, n, _ptr(dy), opt(bn_z), opt(bnb),
-                          pitch, seg_off, _ptr(idx), _ptr(weight), opt(rel), _ptr(d_table), opt(part),
-                          segs, seg_len, _ptr(ws), need, _stream(dy))
-            elif bnb is not None:
-                _lib.call("nesie_blend_conv_backward_bn", b, c, m, n, _ptr(dy), _ptr(bn_z), _ptr(bnb),
-                          pitch, seg_off, _ptr(idx), _ptr(weight), opt(rel), _ptr(d_table), opt(part),
-                          segs, seg_len, _stream(dy))
-            else:
-                _lib.call("nesie_blend_conv_backward", b, c, m, n, _ptr(dy), pitch, seg_off,
-                          _ptr(idx), _ptr(weight), opt(rel), _ptr(d_table), opt(part), segs, seg_len,
-                          _stream(dy))
-            if part is not None:      # (d_wx arrives zero-filled or empty from its caller: the sum overwrites it)
-                torch.sum(part, 0, out=d_wx)
+        part = None
+        if d_wx is not None:   # one partial per workgroup, summed here
+            runs = _lib.load().nesie_blend_conv_runs(n, segs)
+            part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
+        if bnb is not None:
+            _check(bn_z, bnb); _f32(bn_z, bnb)
+            assert tuple(bn_z.shape) == tuple(dy.shape) and tuple(bnb.shape) == (segs * c, 8)
+        if self.DETERMINISTIC and not self.blend_backward_writes_table(c, n, segs, m):
+            raise RuntimeError(
+                f'blend_conv_backward: no fixed-order form for c={c}, {n // segs} queries per face, '
+                f'{m} seeds (needs c in 64..256 step 64, faces of whole 64-query tiles, <= 2047 '
+                'seeds); HipKernels.set_deterministic(False) selects the atomic scatter')
+        if self.blend_backward_writes_table(c, n, segs, m):
+            assert seg_off == c or segs == 1, 'staged form: one column block per face'
+            need = _lib.load().nesie_blend_conv_backward_workspace_bytes(b, c, n, segs)
+            ws = torch.empty(need, dtype=torch.uint8, device=dy.device)
+            _launch("nesie_blend_conv_backward_staged", dy, b, c, m, n, dy, bn_z, bnb, pitch,
+                    seg_off, idx, weight, rel, d_table, part, segs, seg_len, ws, need)
+        elif bnb is not None:
+            _launch("nesie_blend_conv_backward_bn", dy, b, c, m, n, dy, bn_z, bnb, pitch, seg_off,
+                    idx, weight, rel, d_table, part, segs, seg_len)
+        else:
+            _launch("nesie_blend_conv_backward", dy, b, c, m, n, dy, pitch, seg_off, idx, weight,
+                    rel, d_table, part, segs, seg_len)
+        if part is not None:      # (d_wx arrives zero-filled or empty from its caller: the sum overwrites it)
+            torch.sum(part, 0, out=d_wx)
 
     def blend_conv_bn_forward(self, table, idx, weight, rel, wx, gamma, beta, running_mean,
                               running_var, momentum, eps, out, save_mean, save_invstd, fwd_coef,
@@ -633,14 +567,10 @@ class HipKernels(_BNPoolMixin):
         assert tuple(out.shape) == (b, segs, c, n // segs) and tuple(wx.shape) == (segs, c, 3)
         lib = _lib.load()
         need = lib.nesie_blend_conv_bn_workspace_bytes(b, c, n, segs)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(table.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=table.device)
-            _lib.call("nesie_blend_conv_bn_forward", b, c, m, n, _ptr(table), pitch, c, _ptr(idx),
-                      _ptr(weight), _ptr(rel), _ptr(wx), opt(gamma), opt(beta),
-                      opt(running_mean), opt(running_var), float(momentum), float(eps), _ptr(out),
-                      _ptr(save_mean), _ptr(save_invstd), _ptr(fwd_coef), _ptr(ws), need, segs,
-                      seg_len, _stream(table))
+        ws = _workspace(need, table.device)
+        _launch("nesie_blend_conv_bn_forward", table, b, c, m, n, table, pitch, c, idx, weight, rel,
+                wx, gamma, beta, running_mean, running_var, float(momentum), float(eps), out,
+                save_mean, save_invstd, fwd_coef, ws, need, segs, seg_len)
 
     def blend_conv_bn_backward(self, dy, table, idx, weight, rel, wx, gamma, save_invstd,
                                fwd_coef, d_table, d_wx, dgamma, dbeta, segs, seg_len):
@@ -653,15 +583,12 @@ class HipKernels(_BNPoolMixin):
         lib = _lib.load()
         need = lib.nesie_blend_conv_bn_workspace_bytes(b, c, n, segs)
         runs = lib.nesie_blend_conv_runs(n, segs)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(dy.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dy.device)
-            part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
-            _lib.call("nesie_blend_conv_bn_backward", b, c, m, n, _ptr(dy), _ptr(table), pitch, c,
-                      _ptr(idx), _ptr(weight), _ptr(rel), _ptr(wx), opt(gamma),
-                      _ptr(save_invstd), _ptr(fwd_coef), _ptr(d_table), _ptr(part), _ptr(dgamma),
-                      _ptr(dbeta), _ptr(ws), need, segs, seg_len, _stream(dy))
-            d_wx += part.sum(0)
+        ws = _workspace(need, dy.device)
+        part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
+        _launch("nesie_blend_conv_bn_backward", dy, b, c, m, n, dy, table, pitch, c, idx, weight,
+                rel, wx, gamma, save_invstd, fwd_coef, d_table, part, dgamma, dbeta, ws, need, segs,
+                seg_len)
+        d_wx += part.sum(0)
 
     def three_interpolate_grad_wrapper(self, b, c, n, m, grad_out, idx, weight,
                                        grad_points):
@@ -669,9 +596,8 @@ class HipKernels(_BNPoolMixin):
         _i32(idx)
         assert grad_out.numel() == b * c * n and idx.numel() == b * n * 3
         assert weight.numel() == b * n * 3 and grad_points.numel() == b * c * m
-        with torch.cuda.device(grad_out.device):
-            _lib.call("nesie_three_interpolate_grad_wrapper", b, c, n, m, _ptr(grad_out),
-                      _ptr(idx), _ptr(weight), _ptr(grad_points), _stream(grad_out))
+        _launch("nesie_three_interpolate_grad_wrapper", grad_out, b, c, n, m, grad_out, idx, weight,
+                grad_points)
 
     def sort_vertices_forward(self, vertices, mask, num_valid, idx):
         _check(vertices, mask, num_valid, idx); _f32(vertices); _i32(num_valid, idx)
@@ -680,9 +606,7 @@ class HipKernels(_BNPoolMixin):
         b, n, m, two = vertices.shape
         assert two == 2 and tuple(mask.shape) == (b, n, m)
         assert tuple(num_valid.shape) == (b, n) and tuple(idx.shape) == (b, n, 9)
-        with torch.cuda.device(vertices.device):
-            _lib.call("nesie_sort_vertices_forward", b, n, m, _ptr(vertices), _ptr(mask),
-                      _ptr(num_valid), _ptr(idx), _stream(vertices))
+        _launch("nesie_sort_vertices_forward", vertices, b, n, m, vertices, mask, num_valid, idx)
 
     def points_in_boxes_batch(self, boxes, pts, out):
         _check(boxes, pts, out); _f32(boxes, pts); _i32(out)
@@ -690,9 +614,7 @@ class HipKernels(_BNPoolMixin):
         assert seven == 7 and pts.shape[0] == b and pts.shape[2] == 3
         m = pts.shape[1]
         assert tuple(out.shape) == (b, m, t)
-        with torch.cuda.device(boxes.device):
-            _lib.call("nesie_points_in_boxes_batch", b, t, m, _ptr(boxes), _ptr(pts),
-                      _ptr(out), _stream(boxes))
+        _launch("nesie_points_in_boxes_batch", boxes, b, t, m, boxes, pts, out)
 
     def vote_targets(self, points, gt_boxes, gt_count):
         """points (B,N,C>=3), depth-frame gt_boxes (B,T,7), gt_count (B) int64 -> vote targets
@@ -703,9 +625,8 @@ class HipKernels(_BNPoolMixin):
         assert gt_boxes.shape == (b, t, 7) and gt_count.shape == (b,) and gt_count.dtype == torch.int64
         votes = points.new_empty(b, n, 9)
         masks = torch.empty(b, n, dtype=torch.int64, device=points.device)
-        with torch.cuda.device(points.device):
-            _lib.call("nesie_vote_targets", b, t, n, c, _ptr(gt_boxes) if t else 0,
-                      _ptr(gt_count), _ptr(points), _ptr(votes), _ptr(masks), _stream(points))
+        _launch("nesie_vote_targets", points, b, t, n, c, gt_boxes if t else None, gt_count, points,
+                votes, masks)
         return votes, masks
 
     def group_max_pool_forward(self, x, out, argmax):
@@ -714,18 +635,14 @@ class HipKernels(_BNPoolMixin):
         ns = x.shape[-1]
         rows = x.numel() // ns
         assert out.numel() == rows and argmax.numel() == rows and argmax.dtype == torch.uint8
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_group_max_pool_forward", rows, ns, _ptr(x), _ptr(out),
-                      _ptr(argmax), _stream(x))
+        _launch("nesie_group_max_pool_forward", x, rows, ns, x, out, argmax)
 
     def group_max_pool_backward(self, grad_out, argmax, grad_x):
         _check(grad_out, argmax, grad_x); _f32(grad_out, grad_x)
         ns = grad_x.shape[-1]
         rows = grad_x.numel() // ns
         assert grad_out.numel() == rows and argmax.numel() == rows
-        with torch.cuda.device(grad_x.device):
-            _lib.call("nesie_group_max_pool_backward", rows, ns, _ptr(grad_out),
-                      _ptr(argmax), _ptr(grad_x), _stream(grad_x))
+        _launch("nesie_group_max_pool_backward", grad_x, rows, ns, grad_out, argmax, grad_x)
 
 
     def group_max_pool_backward_add(self, grad_out, argmax, grad_x):
@@ -734,9 +651,7 @@ class HipKernels(_BNPoolMixin):
         ns = grad_x.shape[-1]
         rows = grad_x.numel() // ns
         assert grad_out.numel() == rows and argmax.numel() == rows
-        with torch.cuda.device(grad_x.device):
-            _lib.call("nesie_group_max_pool_backward_add", rows, ns, _ptr(grad_out),
-                      _ptr(argmax), _ptr(grad_x), _stream(grad_x))
+        _launch("nesie_group_max_pool_backward_add", grad_x, rows, ns, grad_out, argmax, grad_x)
 
     def channel_sum(self, x, out=None, ng=1):
         """x (NB, C, P) (batch stride free, each x[n] (C, P) contiguous) -> (ng * C,) sums over the
@@ -749,9 +664,7 @@ class HipKernels(_BNPoolMixin):
             out = torch.empty(ng * c, dtype=torch.float32, device=x.device)
         _check(out); _f32(out)
         assert out.numel() == ng * c
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_channel_sum", nb, ng, c, p, _ptr(x), x.stride(0) if nb > 1 else c * p, _ptr(out),
-                      _stream(x))
+        _launch("nesie_channel_sum", x, nb, ng, c, p, x, x.stride(0) if nb > 1 else c * p, out)
         return out
 
     def lhs_nms_samecls(self, boxes, thr, keep):
@@ -759,9 +672,7 @@ class HipKernels(_BNPoolMixin):
         _check(boxes, keep); _f32(boxes)
         b, k, eight = boxes.shape
         assert eight == 8 and tuple(keep.shape) == (b, k) and keep.dtype == torch.uint8
-        with torch.cuda.device(boxes.device):
-            _lib.call("nesie_lhs_nms_samecls", b, k, _ptr(boxes), float(thr), _ptr(keep),
-                      _stream(boxes))
+        _launch("nesie_lhs_nms_samecls", boxes, b, k, boxes, float(thr), keep)
 
     def iou3d_forward(self, box1, box2, iou, jac):
         """box1, box2 (n,7); iou (n,); jac (n,7) or None."""
@@ -771,9 +682,7 @@ class HipKernels(_BNPoolMixin):
         if jac is not None:
             _check(jac); _f32(jac)
             assert jac.numel() == n * 7
-        with torch.cuda.device(box1.device):
-            _lib.call("nesie_iou3d_forward", n, _ptr(box1), _ptr(box2), _ptr(iou),
-                      0 if jac is None else _ptr(jac), _stream(box1))
+        _launch("nesie_iou3d_forward", box1, n, box1, box2, iou, jac)
 
     def conv_wgrad(self, dy, x, dw, x_coef=None, x_relu=False, bn_z=None, bnb=None):
         """dw (cout, cin) = sum_b dy[b] (cout, P) @ act(x[b]) (cin, P)^T on the matrix cores;
@@ -789,20 +698,15 @@ class HipKernels(_BNPoolMixin):
         assert dy.stride(2) == 1 and dy.stride(1) == p, "each dy[b] must be (cout, P) contiguous"
         lib = _lib.load()
         need = lib.nesie_conv_wgrad_workspace_bytes(b, cout, cin, p)
-        with torch.cuda.device(dy.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dy.device)
-            if bnb is not None:
-                _check(bn_z, bnb); _f32(bn_z, bnb)
-                assert tuple(bn_z.shape) == tuple(dy.shape) and dy.is_contiguous() and tuple(bnb.shape) == (cout, 8)
-                _lib.call("nesie_conv_wgrad_bn", b, cout, cin, p, _ptr(dy), _ptr(bn_z), cout * p, _ptr(bnb),
-                          _ptr(x), x.stride(0) if b > 1 else cin * p,
-                          0 if x_coef is None else _ptr(x_coef), int(bool(x_relu)), _ptr(dw), _ptr(ws),
-                          need, _stream(dy))
-                return
-            _lib.call("nesie_conv_wgrad", b, cout, cin, p, _ptr(dy),
-                      dy.stride(0) if b > 1 else cout * p, _ptr(x),
-                      x.stride(0) if b > 1 else cin * p, 0 if x_coef is None else _ptr(x_coef),
-                      int(bool(x_relu)), _ptr(dw), _ptr(ws), need, _stream(dy))
+        ws = _workspace(need, dy.device)
+        if bnb is not None:
+            _check(bn_z, bnb); _f32(bn_z, bnb)
+            assert tuple(bn_z.shape) == tuple(dy.shape) and dy.is_contiguous() and tuple(bnb.shape) == (cout, 8)
+            _launch("nesie_conv_wgrad_bn", dy, b, cout, cin, p, dy, bn_z, cout * p, bnb, x,
+                    x.stride(0) if b > 1 else cin * p, x_coef, bool(x_relu), dw, ws, need)
+            return
+        _launch("nesie_conv_wgrad", dy, b, cout, cin, p, dy, dy.stride(0) if b > 1 else cout * p, x,
+                x.stride(0) if b > 1 else cin * p, x_coef, bool(x_relu), dw, ws, need)
 
     def pw_wgrad_supported(self, co, ci, p):
         return bool(_lib.load().nesie_pw_wgrad_supported(int(co), int(ci), int(p)))
@@ -834,8 +738,7 @@ class HipKernels(_BNPoolMixin):
         held, done = cls._deferred, []
         if held:
             dev = device if device is not None else held[0][1].device
-            with torch.cuda.device(dev):
-                _lib.call("nesie_pw_wgrad_flush_deferred", torch.cuda.current_stream(dev).cuda_stream)
+            _launch("nesie_pw_wgrad_flush_deferred", torch.device(dev))
             done = [dw for _, dw in held]
             # (under a graph capture the workspaces live in the graph's pool; in eager mode the caching
             # allocator hands a freed block to later launches of this stream only: both orders are safe)
@@ -861,14 +764,12 @@ class HipKernels(_BNPoolMixin):
         lib = _lib.load()
         need = lib.nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
         defer = final and HipKernels._deferred is not None
-        with torch.cuda.device(dy.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dy.device)
-            _lib.call("nesie_pw_wgrad_deferred" if defer else "nesie_pw_wgrad", nb, ng, co, ci, p, _ptr(dy),
-                      dy.stride(0) if nb > 1 else co * p, _ptr(x), x.stride(0) if nb > 1 else ci * p,
-                      0 if x_coef is None else _ptr(x_coef), int(bool(x_relu)), _ptr(dw), _ptr(ws),
-                      need, _stream(dy))
-            if defer:
-                HipKernels._deferred.append((ws, dw))
+        ws = _workspace(need, dy.device)
+        _launch("nesie_pw_wgrad_deferred" if defer else "nesie_pw_wgrad", dy, nb, ng, co, ci, p, dy,
+                dy.stride(0) if nb > 1 else co * p, x, x.stride(0) if nb > 1 else ci * p, x_coef,
+                bool(x_relu), dw, ws, need)
+        if defer:
+            HipKernels._deferred.append((ws, dw))
 
     def pw_bnb_coef(self, part, z_coef, gamma, count, dgamma, dbeta):
         """(channels, 8) reduction coefficients of a BatchNorm + ReLU backward from the partial sums
@@ -879,11 +780,9 @@ class HipKernels(_BNPoolMixin):
         assert dgamma.numel() == ch == dbeta.numel()
         if gamma is not None:
             _check(gamma); _f32(gamma)
-        with torch.cuda.device(part.device):
-            bnb = torch.empty(ch, 8, dtype=torch.float32, device=part.device)
-            _lib.call("nesie_pw_bnb_coef", ch, part.shape[1], float(count), _ptr(part), _ptr(z_coef),
-                      0 if gamma is None else _ptr(gamma), _ptr(bnb), _ptr(dgamma), _ptr(dbeta),
-                      _stream(part))
+        bnb = torch.empty(ch, 8, dtype=torch.float32, device=part.device)
+        _launch("nesie_pw_bnb_coef", part, ch, part.shape[1], float(count), part, z_coef, gamma,
+                bnb, dgamma, dbeta)
         return bnb
 
     def pw_wgrad_bn_supported(self, co, ci, p):
@@ -917,22 +816,44 @@ class HipKernels(_BNPoolMixin):
         lib = _lib.load()
         need = lib.nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
         defer = final and HipKernels._deferred is not None
-        with torch.cuda.device(da.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=da.device)
-            cws = torch.empty(ng * co, 8, dtype=torch.float32, device=da.device)
-            if defer:
-                HipKernels._deferred.append((ws, dw))
-            _lib.call("nesie_pw_wgrad_bn_backward_deferred" if defer else "nesie_pw_wgrad_bn_backward",
-                      nb, ng, co, ci, p, _ptr(da), _ptr(z), co * p,
-                      _ptr(z_coef), 0 if gamma is None else _ptr(gamma), _ptr(part), part.shape[1],
-                      _ptr(x), x.stride(0) if nb > 1 else ci * p, 0 if x_coef is None else _ptr(x_coef),
-                      int(bool(x_relu)), _ptr(dz), _ptr(dw), _ptr(dgamma), _ptr(dbeta), _ptr(cws),
-                      0 if d_row_bias is None else _ptr(d_row_bias), int(group), _ptr(ws), need,
-                      _stream(da))
+        ws = _workspace(need, da.device)
+        cws = torch.empty(ng * co, 8, dtype=torch.float32, device=da.device)
+        if defer:
+            HipKernels._deferred.append((ws, dw))
+        _launch("nesie_pw_wgrad_bn_backward_deferred" if defer else "nesie_pw_wgrad_bn_backward",
+                da, nb, ng, co, ci, p, da, z, co * p, z_coef, gamma, part, part.shape[1], x,
+                x.stride(0) if nb > 1 else ci * p, x_coef, bool(x_relu), dz, dw, dgamma, dbeta, cws,
+                d_row_bias, int(group), ws, need)
 
     @staticmethod
     def conv_wgrad_supported(cout, cin):
         return (cout <= 128 and cin <= 288) or (cout <= 256 and cin <= 128)
+
+    @staticmethod
+    def _bn_pool_ws(x):
+        b, c, m, ns = x.shape
+        need = _lib.load().nesie_bn_workspace_bytes(b, c, m * ns)
+        return _workspace(need, x.device), need
+
+    def bn_relu_maxpool_forward(self, x, gamma, beta, running_mean, running_var, momentum, eps,
+                                pooled, argmax, save_mean, save_invstd, fwd_coef):
+        """x (B, C, M, ns) -> pooled (B, C, M) fp32, argmax (B, C, M) uint8."""
+        _check(x, pooled, argmax, save_mean, save_invstd, fwd_coef); _f32(x, pooled)
+        b, c, m, ns = x.shape
+        assert tuple(pooled.shape) == (b, c, m) and argmax.dtype == torch.uint8
+        ws, need = self._bn_pool_ws(x)
+        _launch("nesie_bn_relu_maxpool_forward", x, b, c, m, ns, x, gamma, beta, running_mean,
+                running_var, float(momentum), float(eps), pooled, argmax, save_mean, save_invstd,
+                fwd_coef, ws, need)
+
+    def bn_relu_maxpool_backward(self, grad_pooled, argmax, x, pooled, gamma, save_invstd,
+                                 fwd_coef, dx, dgamma, dbeta):
+        _check(grad_pooled, argmax, x, pooled, dx); _f32(grad_pooled, x, pooled, dx)
+        b, c, m, ns = x.shape
+        assert tuple(grad_pooled.shape) == (b, c, m) and dx.shape == x.shape
+        ws, need = self._bn_pool_ws(x)
+        _launch("nesie_bn_relu_maxpool_backward", x, b, c, m, ns, grad_pooled, argmax, x, pooled,
+                gamma, save_invstd, fwd_coef, dx, dgamma, dbeta, ws, need)
 
     def bn_relu_forward(self, x, gamma, beta, running_mean, running_var, momentum, eps, relu,
                         y, save_mean, save_invstd, fwd_coef, row_bias=None, pre_partial=None):
@@ -943,15 +864,11 @@ class HipKernels(_BNPoolMixin):
         p = x.numel() // (b * c) if b * c else 0
         group = _row_bias_group(x, row_bias)
         need = _lib.load().nesie_bn_workspace_bytes(b, c, p)
-        with torch.cuda.device(x.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
-            opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-            _lib.call("nesie_bn_relu_forward", b, c, p, _ptr(x), opt(gamma), opt(beta),
-                      opt(running_mean), opt(running_var), float(momentum), float(eps),
-                      int(bool(relu)), _ptr(y), _ptr(save_mean), _ptr(save_invstd),
-                      _ptr(fwd_coef), opt(row_bias), group, opt(pre_partial),
-                      0 if pre_partial is None else pre_partial.numel() // (2 * c),
-                      _ptr(ws), need, _stream(x))
+        ws = _workspace(need, x.device)
+        _launch("nesie_bn_relu_forward", x, b, c, p, x, gamma, beta, running_mean, running_var,
+                float(momentum), float(eps), bool(relu), y, save_mean, save_invstd, fwd_coef,
+                row_bias, group, pre_partial,
+                0 if pre_partial is None else pre_partial.numel() // (2 * c), ws, need)
 
     def pw_supported(self, k, cout, p):
         return bool(_lib.load().nesie_pw_supported(int(k), int(cout), int(p)))
@@ -973,7 +890,6 @@ class HipKernels(_BNPoolMixin):
         assert w.dim() == 3 and w.shape[0] == ng and w.shape[2] == k and nb % ng == 0
         cout = w.shape[1]
         assert x.is_cuda and x.stride(2) == 1 and x.stride(1) == p, "each x[n] must be (K, P) contiguous"
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
         if y is not None:
             _f32(y)
             assert y.is_cuda and tuple(y.shape) == (nb, cout, p) and y.stride(2) == 1 \
@@ -1002,14 +918,11 @@ class HipKernels(_BNPoolMixin):
                     _check(t)
                     assert t.dtype == torch.uint8 and t.numel() == nb * cout * (p // pool_group)
             assert (pmin is not None) == bool(pool_min)
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_pw_layer_forward", nb, ng, k, cout, p, _ptr(x),
-                      x.stride(0) if nb > 1 else k * p, _ptr(w), w.stride(0) if ng > 1 else 0,
-                      w.stride(1), w.stride(2), opt(in_coef), int(bool(in_relu)), opt(row_bias),
-                      int(rb_group), opt(bias), opt(y),
-                      y.stride(0) if (y is not None and nb > 1) else cout * p, opt(stat_part),
-                      int(pool_group),
-                      int(bool(pool_min)), opt(pmax), opt(pmin), opt(amax), opt(amin), _stream(x))
+        _launch("nesie_pw_layer_forward", x, nb, ng, k, cout, p, x,
+                x.stride(0) if nb > 1 else k * p, w, w.stride(0) if ng > 1 else 0, w.stride(1),
+                w.stride(2), in_coef, bool(in_relu), row_bias, int(rb_group), bias, y,
+                y.stride(0) if (y is not None and nb > 1) else cout * p, stat_part, int(pool_group),
+                bool(pool_min), pmax, pmin, amax, amin)
 
     # ---- SA1's first layer without its output tensor (include/nesie_ops.h, "round 5: the first
     # shared-MLP layer ... WITHOUT its output tensor")
@@ -1034,10 +947,8 @@ class HipKernels(_BNPoolMixin):
         cout = w.shape[0]
         assert tuple(w.shape) == (cout, 64) and tuple(y.shape) == (nb, cout, p) and tuple(in_coef.shape) == (64, 4)
         assert tuple(stat_part.shape) == (1, self.pw_stat_slots(nb, 1, 64, cout, p), cout, 4)
-        with torch.cuda.device(x4.device):
-            _lib.call("nesie_pw_layer_forward_k4", nb, cout, p, _ptr(x4), x4.stride(0) if nb > 1 else 4 * p,
-                      _ptr(w0), _ptr(w), w.stride(0), w.stride(1), _ptr(in_coef), _ptr(y), cout * p,
-                      _ptr(stat_part), _stream(x4))
+        _launch("nesie_pw_layer_forward_k4", x4, nb, cout, p, x4, x4.stride(0) if nb > 1 else 4 * p,
+                w0, w, w.stride(0), w.stride(1), in_coef, y, cout * p, stat_part)
 
     def pw_dgrad_bn_reduce_k4(self, dy, w, x4, w0, z_coef):
         """The reductions of ``pw_dgrad_bn_reduce`` for a layer whose input was relu(bn(W0 . x4)),
@@ -1051,10 +962,9 @@ class HipKernels(_BNPoolMixin):
         slots = self.pw_stat_slots(nb, 1, k, 64, p)
         part = torch.empty(64, slots, 2, dtype=torch.float32, device=dy.device)
         g_part = torch.empty(64, slots, 4, dtype=torch.float32, device=dy.device)
-        with torch.cuda.device(dy.device):
-            _lib.call("nesie_pw_dgrad_bn_reduce_k4", nb, k, p, _ptr(dy), dy.stride(0) if nb > 1 else k * p,
-                      _ptr(w), w.stride(0), w.stride(1), _ptr(x4), x4.stride(0) if nb > 1 else 4 * p,
-                      _ptr(w0), _ptr(z_coef), _ptr(part), _ptr(g_part), _stream(dy))
+        _launch("nesie_pw_dgrad_bn_reduce_k4", dy, nb, k, p, dy, dy.stride(0) if nb > 1 else k * p,
+                w, w.stride(0), w.stride(1), x4, x4.stride(0) if nb > 1 else 4 * p, w0, z_coef,
+                part, g_part)
         return part, g_part
 
     def pw_wgrad_bn_backward_k4(self, da, z, z_coef, gamma, part, x4, w0, x_coef, dw, dgamma, dbeta,
@@ -1069,15 +979,13 @@ class HipKernels(_BNPoolMixin):
             _check(gamma); _f32(gamma)
         need = _lib.load().nesie_pw_wgrad_workspace_bytes(nb, 1, 64, 64, p)
         defer = final and HipKernels._deferred is not None
-        with torch.cuda.device(da.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=da.device)
-            cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
-            if defer:
-                HipKernels._deferred.append((ws, dw))
-            _lib.call("nesie_pw_wgrad_bn_backward_k4", nb, p, _ptr(da), _ptr(z), 64 * p, _ptr(z_coef),
-                      0 if gamma is None else _ptr(gamma), _ptr(part), part.shape[1], _ptr(x4),
-                      x4.stride(0) if nb > 1 else 4 * p, _ptr(w0), _ptr(x_coef), _ptr(da), _ptr(dw),
-                      _ptr(dgamma), _ptr(dbeta), _ptr(cws), _ptr(ws), need, int(defer), _stream(da))
+        ws = _workspace(need, da.device)
+        cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
+        if defer:
+            HipKernels._deferred.append((ws, dw))
+        _launch("nesie_pw_wgrad_bn_backward_k4", da, nb, p, da, z, 64 * p, z_coef, gamma, part,
+                part.shape[1], x4, x4.stride(0) if nb > 1 else 4 * p, w0, x_coef, da, dw, dgamma,
+                dbeta, cws, ws, need, int(defer))
 
     def pw_wgrad_bn_backward_k4_fused(self, da, z, z_coef, gamma, part, x4, w0, x_coef, w, dw, dgamma, dbeta,
                                       final=False):
@@ -1094,18 +1002,15 @@ class HipKernels(_BNPoolMixin):
         need = lib.nesie_pw_wgrad_workspace_bytes(nb, 1, 64, 64, p)
         slots = lib.nesie_pw_wgrad_bn_backward_k4_slots(nb, p)
         defer = final and HipKernels._deferred is not None
-        with torch.cuda.device(da.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=da.device)
-            cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
-            in_part = torch.empty(64, slots, 2, dtype=torch.float32, device=da.device)
-            in_gpart = torch.empty(64, slots, 4, dtype=torch.float32, device=da.device)
-            if defer:
-                HipKernels._deferred.append((ws, dw))
-            _lib.call("nesie_pw_wgrad_bn_backward_k4_fused", nb, p, _ptr(da), _ptr(z), 64 * p, _ptr(z_coef),
-                      0 if gamma is None else _ptr(gamma), _ptr(part), part.shape[1], _ptr(x4),
-                      x4.stride(0) if nb > 1 else 4 * p, _ptr(w0), _ptr(x_coef), _ptr(w), _ptr(dw),
-                      _ptr(dgamma), _ptr(dbeta), _ptr(cws), _ptr(in_part), _ptr(in_gpart), _ptr(ws), need,
-                      int(defer), _stream(da))
+        ws = _workspace(need, da.device)
+        cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
+        in_part = torch.empty(64, slots, 2, dtype=torch.float32, device=da.device)
+        in_gpart = torch.empty(64, slots, 4, dtype=torch.float32, device=da.device)
+        if defer:
+            HipKernels._deferred.append((ws, dw))
+        _launch("nesie_pw_wgrad_bn_backward_k4_fused", da, nb, p, da, z, 64 * p, z_coef, gamma,
+                part, part.shape[1], x4, x4.stride(0) if nb > 1 else 4 * p, w0, x_coef, w, dw,
+                dgamma, dbeta, cws, in_part, in_gpart, ws, need, int(defer))
         return in_part, in_gpart
 
     def k4_moments(self, x4):
@@ -1114,19 +1019,16 @@ class HipKernels(_BNPoolMixin):
         nb, c, p = x4.shape
         assert x4.is_cuda and c == 4 and x4.stride(2) == 1 and x4.stride(1) == p
         need = _lib.load().nesie_k4_moments_bytes()
-        with torch.cuda.device(x4.device):
-            mom = torch.empty(need // 160, 20, dtype=torch.float64, device=x4.device)
-            _lib.call("nesie_k4_moments", nb, p, _ptr(x4), x4.stride(0) if nb > 1 else 4 * p, _ptr(mom), _stream(x4))
+        mom = torch.empty(need // 160, 20, dtype=torch.float64, device=x4.device)
+        _launch("nesie_k4_moments", x4, nb, p, x4, x4.stride(0) if nb > 1 else 4 * p, mom)
         return mom
 
     def k4_stat_finalize(self, mom, w0, gamma, beta, running_mean, running_var, momentum, eps, count, coef):
         """Training-mode BatchNorm coefficients of W0 . X4 from the moments of X4 (nesie_k4_stat_finalize)."""
         _check(mom, w0, coef); _f32(w0, coef)
         assert mom.dtype == torch.float64 and tuple(w0.shape) == (64, 4) and tuple(coef.shape) == (64, 4)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(mom.device):
-            _lib.call("nesie_k4_stat_finalize", float(count), _ptr(mom), _ptr(w0), opt(gamma), opt(beta),
-                      opt(running_mean), opt(running_var), float(momentum), float(eps), _ptr(coef), _stream(mom))
+        _launch("nesie_k4_stat_finalize", mom, float(count), mom, w0, gamma, beta, running_mean,
+                running_var, float(momentum), float(eps), coef)
 
     def k4_first_layer_wgrad(self, mom, w0, bnb, g_part, dw):
         """dW0 (64, 4) from the reductions (nesie_k4_first_layer_wgrad): mom from ``k4_moments``, bnb (64, 8)
@@ -1134,9 +1036,7 @@ class HipKernels(_BNPoolMixin):
         _check(mom, w0, bnb, g_part, dw); _f32(w0, bnb, g_part, dw)
         assert mom.dtype == torch.float64 and tuple(w0.shape) == (64, 4)
         assert tuple(bnb.shape) == (64, 8) and g_part.shape[0] == 64 and g_part.shape[2] == 4 and dw.numel() == 256
-        with torch.cuda.device(mom.device):
-            _lib.call("nesie_k4_first_layer_wgrad", _ptr(mom), _ptr(w0), _ptr(bnb), _ptr(g_part), g_part.shape[1],
-                      _ptr(dw), _stream(mom))
+        _launch("nesie_k4_first_layer_wgrad", mom, mom, w0, bnb, g_part, g_part.shape[1], dw)
 
     def pw_dgrad_bn_reduce(self, dy, w, z, z_coef, da, ng=1):
         """da[n] = W[n % ng] . dy[n] (w = the transposed weight view (ng, Cin, Cout)) plus the
@@ -1153,10 +1053,9 @@ class HipKernels(_BNPoolMixin):
         part = torch.empty(ng * cout, self.pw_stat_slots(nb, ng, k, cout, p), 2,
                            dtype=torch.float32, device=dy.device)
         bs = lambda t, rows: t.stride(0) if nb > 1 else rows * p  # noqa: E731
-        with torch.cuda.device(dy.device):
-            _lib.call("nesie_pw_dgrad_bn_reduce", nb, ng, k, cout, p, _ptr(dy), bs(dy, k), _ptr(w),
-                      w.stride(0) if ng > 1 else 0, w.stride(1), w.stride(2), _ptr(da),
-                      bs(da, cout), _ptr(z), bs(z, cout), _ptr(z_coef), _ptr(part), _stream(dy))
+        _launch("nesie_pw_dgrad_bn_reduce", dy, nb, ng, k, cout, p, dy, bs(dy, k), w,
+                w.stride(0) if ng > 1 else 0, w.stride(1), w.stride(2), da, bs(da, cout), z,
+                bs(z, cout), z_coef, part)
         return part
 
     def bn_relu_backward_apply(self, dy, x, gamma, save_invstd, fwd_coef, partial, dx, dgamma,
@@ -1171,12 +1070,8 @@ class HipKernels(_BNPoolMixin):
         if d_row_bias is not None:
             _check(d_row_bias); _f32(d_row_bias)
             assert group and d_row_bias.numel() == b * c * (p // group)
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(x.device):
-            _lib.call("nesie_bn_relu_backward_apply", b, c, p, _ptr(dy), _ptr(x), opt(gamma),
-                      opt(save_invstd), _ptr(fwd_coef), _ptr(partial), int(partial.shape[1]),
-                      _ptr(dx), opt(dgamma), opt(dbeta), int(group or 1), opt(d_row_bias),
-                      _stream(x))
+        _launch("nesie_bn_relu_backward_apply", x, b, c, p, dy, x, gamma, save_invstd, fwd_coef,
+                partial, int(partial.shape[1]), dx, dgamma, dbeta, int(group or 1), d_row_bias)
 
     def vote_loss_forward(self, seed, vote, seed_idx, mask, targets, w_dst, ticket):
         """-> (loss scalar, sign (B,N,3), scale scalar) (nesie_vote_loss_forward)."""
@@ -1191,19 +1086,14 @@ class HipKernels(_BNPoolMixin):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         scale = torch.empty((), dtype=torch.float32, device=dev)
         partial = torch.empty(64, 2, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("nesie_vote_loss_forward", b, n, npts, gps, _ptr(seed), _ptr(vote),
-                      _ptr(seed_idx), _ptr(mask), _ptr(targets), float(w_dst), _ptr(sign),
-                      _ptr(loss), _ptr(scale), _ptr(partial), _ptr(ticket),
-                      _stream(seed))
+        _launch("nesie_vote_loss_forward", seed, b, n, npts, gps, seed, vote, seed_idx, mask,
+                targets, float(w_dst), sign, loss, scale, partial, ticket)
         return loss, sign, scale
 
     def vote_loss_backward(self, g, scale, sign):
         _check(g, scale, sign); _f32(g, scale, sign)
         d = torch.empty_like(sign)
-        with torch.cuda.device(sign.device):
-            _lib.call("nesie_vote_loss_backward", sign.numel(), _ptr(g), _ptr(scale), _ptr(sign),
-                      _ptr(d), _stream(sign))
+        _launch("nesie_vote_loss_backward", sign, sign.numel(), g, scale, sign, d)
         return d
 
     def proposal_jitter(self, bbox, noise_c, noise_s, sigma, size_bias, zero_heading):
@@ -1214,10 +1104,8 @@ class HipKernels(_BNPoolMixin):
         dev = bbox.device
         f32 = lambda *s_: torch.empty(*s_, dtype=torch.float32, device=dev)  # noqa: E731
         ca, sa, ha, jb = f32(b, 2 * k, 3), f32(b, 2 * k, 3), f32(b, 2 * k), f32(b, k, 7)
-        with torch.cuda.device(dev):
-            _lib.call("nesie_proposal_jitter", b, k, _ptr(bbox), _ptr(noise_c), _ptr(noise_s),
-                      float(sigma), float(size_bias), int(bool(zero_heading)), _ptr(ca), _ptr(sa),
-                      _ptr(ha), _ptr(jb), _stream(bbox))
+        _launch("nesie_proposal_jitter", bbox, b, k, bbox, noise_c, noise_s, float(sigma),
+                float(size_bias), bool(zero_heading), ca, sa, ha, jb)
         return ca, sa, ha, jb
 
     def side_prob_stats(self, probs, copies):
@@ -1227,9 +1115,7 @@ class HipKernels(_BNPoolMixin):
         b, six, bins, k = probs.shape
         assert six == 6 and bins >= 5
         out = torch.empty(6, b, bins + 5, copies * k, dtype=torch.float32, device=probs.device)
-        with torch.cuda.device(probs.device):
-            _lib.call("nesie_side_prob_stats", b, bins, k, int(copies), _ptr(probs), _ptr(out),
-                      _stream(probs))
+        _launch("nesie_side_prob_stats", probs, b, bins, k, int(copies), probs, out)
         return out
 
     def flat_adamw_step(self, param, grad, exp_avg, exp_avg_sq, step, lr, betas, eps, weight_decay,
@@ -1246,19 +1132,13 @@ class HipKernels(_BNPoolMixin):
         if hyper is not None:
             _check(hyper); _f32(hyper)
             assert hyper.numel() == 2 and hyper.is_contiguous()
-            with torch.cuda.device(param.device):
-                _lib.call("nesie_flat_adamw_step_dev", n, _ptr(param), _ptr(grad), _ptr(exp_avg),
-                          _ptr(exp_avg_sq), _ptr(step), _ptr(hyper), float(betas[0]),
-                          float(betas[1]), float(eps), float(max_norm or 0.0),
-                          0 if grad_norm_out is None else _ptr(grad_norm_out), _ptr(ws), need,
-                          _stream(param))
+            _launch("nesie_flat_adamw_step_dev", param, n, param, grad, exp_avg, exp_avg_sq, step,
+                    hyper, float(betas[0]), float(betas[1]), float(eps), float(max_norm or 0.0),
+                    grad_norm_out, ws, need)
             return
-        with torch.cuda.device(param.device):
-            _lib.call("nesie_flat_adamw_step", n, _ptr(param), _ptr(grad), _ptr(exp_avg),
-                      _ptr(exp_avg_sq), _ptr(step), float(lr), float(betas[0]), float(betas[1]),
-                      float(eps), float(weight_decay), float(max_norm or 0.0),
-                      0 if grad_norm_out is None else _ptr(grad_norm_out), _ptr(ws), need,
-                      _stream(param))
+        _launch("nesie_flat_adamw_step", param, n, param, grad, exp_avg, exp_avg_sq, step,
+                float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                float(max_norm or 0.0), grad_norm_out, ws, need)
 
     # ---- Nesie head: targets and loss terms (include/nesie_head_ops.h) -----------------------
     def head_targets(self, agg, gt_boxes, gt_labels, gt_count, gt_valid, pos_thr, neg_thr):
@@ -1274,13 +1154,10 @@ class HipKernels(_BNPoolMixin):
         out = dict(assignment=i64(b, k), obj_targets=i64(b, k), obj_weights=f32(b, k),
                    mask_targets=i64(b, k), bbox_targets=f32(b, k, 7), center_targets=f32(b, t, 3),
                    box_weights=f32(b, k), valid_weights=f32(b, t))
-        with torch.cuda.device(dev):
-            _lib.call("nesie_head_targets", b, k, t, _ptr(agg), _ptr(gt_boxes), _ptr(gt_labels),
-                      _ptr(gt_count), _ptr(gt_valid), float(pos_thr), float(neg_thr),
-                      _ptr(out['assignment']), _ptr(out['obj_targets']), _ptr(out['obj_weights']),
-                      _ptr(out['mask_targets']), _ptr(out['bbox_targets']),
-                      _ptr(out['center_targets']), _ptr(out['box_weights']),
-                      _ptr(out['valid_weights']), _stream(agg))
+        _launch("nesie_head_targets", agg, b, k, t, agg, gt_boxes, gt_labels, gt_count, gt_valid,
+                float(pos_thr), float(neg_thr), out['assignment'], out['obj_targets'],
+                out['obj_weights'], out['mask_targets'], out['bbox_targets'], out['center_targets'],
+                out['box_weights'], out['valid_weights'])
         return out
 
     def head_loss_forward(self, cls, bbox, surface, side, iou_s, iou, iou_j, tg, config, ticket,
@@ -1311,23 +1188,19 @@ class HipKernels(_BNPoolMixin):
         if quality is not None:
             _check(quality); _f32(quality)
             assert quality.numel() == b * k * 6
-            head = ("nesie_head_loss_forward_unsup", b, k, t, c, _ptr(cls), _ptr(bbox), _ptr(surface),
-                    _ptr(side), _ptr(iou_s), _ptr(iou), _ptr(quality), int(bool(detach_sigma)))
+            head = ("nesie_head_loss_forward_unsup", cls, b, k, t, c, cls, bbox, surface, side, iou_s,
+                    iou, quality, bool(detach_sigma))
         elif sigma_mode:      # the SAQE head's supervised losses: constant (1) or no (2) uncertainties
-            head = ("nesie_head_loss_forward_sigma", int(sigma_mode), b, k, t, c, _ptr(cls), _ptr(bbox),
-                    _ptr(surface), _ptr(side), _ptr(iou_s), _ptr(iou), _ptr(iou_j))
+            head = ("nesie_head_loss_forward_sigma", cls, int(sigma_mode), b, k, t, c, cls, bbox,
+                    surface, side, iou_s, iou, iou_j)
         else:
-            head = ("nesie_head_loss_forward", b, k, t, c, _ptr(cls), _ptr(bbox), _ptr(surface),
-                    _ptr(side), _ptr(iou_s), _ptr(iou), _ptr(iou_j))
-        with torch.cuda.device(dev):
-            _lib.call(*head, _ptr(tg['obj_targets']),
-                      _ptr(tg['mask_targets']), _ptr(tg['obj_weights']), _ptr(tg['box_weights']),
-                      _ptr(tg['bbox_targets']), _ptr(tg['center_targets']),
-                      _ptr(tg['valid_weights']), ctypes.cast(cfg, ctypes.c_void_p), _ptr(loss),
-                      _ptr(sv['cls']), _ptr(sv['centre']), _ptr(sv['surface']), _ptr(sv['iou']),
-                      _ptr(sv['iou_s']), _ptr(sv['side_surf']), _ptr(sv['side_iou']),
-                      _ptr(sv['side_pred']), _ptr(sv['sem_pick']), _ptr(kstar), _ptr(dmin),
-                      _ptr(partial), _ptr(ticket), _stream(cls))
+            head = ("nesie_head_loss_forward", cls, b, k, t, c, cls, bbox, surface, side, iou_s, iou,
+                    iou_j)
+        _launch(*head, tg['obj_targets'], tg['mask_targets'], tg['obj_weights'], tg['box_weights'],
+                tg['bbox_targets'], tg['center_targets'], tg['valid_weights'],
+                ctypes.cast(cfg, ctypes.c_void_p), loss, sv['cls'], sv['centre'], sv['surface'],
+                sv['iou'], sv['iou_s'], sv['side_surf'], sv['side_iou'], sv['side_pred'],
+                sv['sem_pick'], kstar, dmin, partial, ticket)
         return loss, sv
 
     def saqe_extra_forward(self, robj, rot, bbox, bbox_t, jsurf, side, tg, sem_pick, config, sup,
@@ -1347,13 +1220,10 @@ class HipKernels(_BNPoolMixin):
         loss, partial = f32(4), f32((b * k + 63) // 64, 4)
         wmax = tg['box_weights'].max().reshape(1)
         cfg = (ctypes.c_float * 7)(*[float(v) for v in config])
-        with torch.cuda.device(dev):
-            _lib.call("nesie_saqe_extra_loss_forward", b, k, c, int(bool(sup)), _ptr(robj), _ptr(rot),
-                      _ptr(bbox), _ptr(bbox_t), _ptr(jsurf), _ptr(side), _ptr(tg['obj_targets']),
-                      _ptr(tg['mask_targets']), _ptr(tg['obj_weights']), _ptr(tg['box_weights']),
-                      _ptr(wmax), _ptr(sem_pick), ctypes.cast(cfg, ctypes.c_void_p), _ptr(loss),
-                      _ptr(sv['robj']), _ptr(sv['angle']), _ptr(sv['rot']), _ptr(sv['sidej']),
-                      _ptr(partial), _ptr(ticket), _stream(rot))
+        _launch("nesie_saqe_extra_loss_forward", rot, b, k, c, bool(sup), robj, rot, bbox, bbox_t,
+                jsurf, side, tg['obj_targets'], tg['mask_targets'], tg['obj_weights'],
+                tg['box_weights'], wmax, sem_pick, ctypes.cast(cfg, ctypes.c_void_p), loss,
+                sv['robj'], sv['angle'], sv['rot'], sv['sidej'], partial, ticket)
         return loss, sv
 
     def saqe_extra_backward(self, g, label, sv, k):
@@ -1364,10 +1234,8 @@ class HipKernels(_BNPoolMixin):
         out = dict(robj=torch.empty_like(sv['robj']), angle=torch.empty_like(sv['angle']),
                    rot=torch.empty_like(sv['rot']),
                    side=torch.zeros(6, b, c, k2, dtype=torch.float32, device=dev))
-        with torch.cuda.device(dev):
-            _lib.call("nesie_saqe_extra_loss_backward", b, k, c, _ptr(g), _ptr(label), _ptr(sv['robj']),
-                      _ptr(sv['angle']), _ptr(sv['rot']), _ptr(sv['sidej']), _ptr(out['robj']),
-                      _ptr(out['angle']), _ptr(out['rot']), _ptr(out['side']), _stream(g))
+        _launch("nesie_saqe_extra_loss_backward", g, b, k, c, g, label, sv['robj'], sv['angle'],
+                sv['rot'], sv['sidej'], out['robj'], out['angle'], out['rot'], out['side'])
         return out
 
     def head_loss_backward(self, g, label, sv, k):
@@ -1382,13 +1250,10 @@ class HipKernels(_BNPoolMixin):
                    surface=torch.empty_like(sv['surface']), iou=torch.empty_like(sv['iou']),
                    iou_s=torch.empty_like(sv['iou_s']),
                    side=torch.zeros(6, b, c, 2 * k, dtype=torch.float32, device=dev))
-        with torch.cuda.device(dev):
-            _lib.call("nesie_head_loss_backward", b, k, c, _ptr(g), _ptr(label), _ptr(sv['sem_pick']),
-                      _ptr(sv['cls']), _ptr(sv['centre']), _ptr(sv['surface']), _ptr(sv['iou']),
-                      _ptr(sv['iou_s']), _ptr(sv['side_surf']), _ptr(sv['side_iou']),
-                      _ptr(sv['side_pred']), _ptr(out['cls']), _ptr(out['bbox']),
-                      _ptr(out['surface']), _ptr(out['iou']), _ptr(out['iou_s']), _ptr(out['side']),
-                      _stream(g))
+        _launch("nesie_head_loss_backward", g, b, k, c, g, label, sv['sem_pick'], sv['cls'],
+                sv['centre'], sv['surface'], sv['iou'], sv['iou_s'], sv['side_surf'],
+                sv['side_iou'], sv['side_pred'], out['cls'], out['bbox'], out['surface'],
+                out['iou'], out['iou_s'], out['side'])
         return out
 
     def pw_stats_finalize(self, stat_part, gamma, beta, running_mean, running_var, momentum, eps,
@@ -1400,11 +1265,8 @@ class HipKernels(_BNPoolMixin):
         ng, nslots, cout, _ = stat_part.shape
         assert tuple(coef.shape) == (ng * cout, 4)
         assert chan_bias is None or (chan_bias.numel() == ng * cout and chan_bias.is_contiguous())
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(coef.device):
-            _lib.call("nesie_pw_stats_finalize", ng * cout, cout, nslots, _ptr(stat_part), opt(gamma),
-                      opt(beta), opt(running_mean), opt(running_var), float(momentum), float(eps),
-                      _ptr(coef), opt(chan_bias), _stream(coef))
+        _launch("nesie_pw_stats_finalize", coef, ng * cout, cout, nslots, stat_part, gamma, beta,
+                running_mean, running_var, float(momentum), float(eps), coef, chan_bias)
 
     def pw_pool_finish(self, ng, p, group, pool_group, pool_out, coef, relu, pooled, argmax, zstar=None):
         """partial extrema (NB, C, P / pool_group) -> pooled (NB, C, P / group) float,
@@ -1413,18 +1275,14 @@ class HipKernels(_BNPoolMixin):
         _check(pmax, amax, pooled, argmax); _f32(pmax, pooled)
         nb, c = pooled.shape[:2]
         assert pooled.numel() == nb * c * (p // group) and argmax.dtype == torch.uint8
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(pooled.device):
-            if zstar is not None:
-                _check(zstar); _f32(zstar)
-                assert zstar.numel() == pooled.numel()
-                _lib.call("nesie_pw_pool_finish_z", nb, ng, c, p, group, pool_group, _ptr(pmax), opt(pmin),
-                          _ptr(amax), opt(amin), opt(coef), int(bool(relu)), _ptr(pooled),
-                          _ptr(argmax), _ptr(zstar), _stream(pooled))
-                return
-            _lib.call("nesie_pw_pool_finish", nb, ng, c, p, group, pool_group, _ptr(pmax), opt(pmin),
-                      _ptr(amax), opt(amin), opt(coef), int(bool(relu)), _ptr(pooled),
-                      _ptr(argmax), _stream(pooled))
+        if zstar is not None:
+            _check(zstar); _f32(zstar)
+            assert zstar.numel() == pooled.numel()
+            _launch("nesie_pw_pool_finish_z", pooled, nb, ng, c, p, group, pool_group, pmax, pmin,
+                    amax, amin, coef, bool(relu), pooled, argmax, zstar)
+            return
+        _launch("nesie_pw_pool_finish", pooled, nb, ng, c, p, group, pool_group, pmax, pmin, amax,
+                amin, coef, bool(relu), pooled, argmax)
 
     # ---- pooled tail without the dense pre-pool tensor (csrc/pool_tail.hip) ---------------------
     def pool_tail_supported(self, k, c, p, ns):
@@ -1447,26 +1305,22 @@ class HipKernels(_BNPoolMixin):
         dev = g.device
         f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         sizes = (ctypes.c_int * 2)()
-        _lib.call("nesie_pool_tail_sizes", nb, k, c, p, ctypes.addressof(sizes))
+        _lib.call("nesie_pool_tail_sizes", nb, k, c, p, ctypes.addressof(sizes))   # host only: no stream
         nslots, nparts = int(sizes[0]), int(sizes[1])
         ab, ent, wcat, c0 = f(c, 4), f(nb, m, c, 2), f(k, c + k), f(k)
         da, part = f(nb, k, p), f(k, nslots, 2)
         zbs = z_prev.stride(0) if nb > 1 else k * p
-        with torch.cuda.device(dev):
-            st = _stream(g)
-            _lib.call("nesie_pool_tail_prepare", nb, c, m, ns, k, _ptr(g), _ptr(pooled), _ptr(zstar),
-                      _ptr(argmax), _ptr(coef), _ptr(gamma), _ptr(w), _ptr(dgamma), _ptr(dbeta),
-                      _ptr(ab), _ptr(ent), _ptr(wcat), _ptr(c0), st)
-            _lib.call("nesie_pool_tail_dgrad", nb, k, c, p, ns, _ptr(z_prev), zbs, _ptr(coef_prev),
-                      _ptr(wcat), _ptr(c0), _ptr(ent), _ptr(da), k * p, _ptr(part), st)
-            if dw is not None:
-                _check(dw); _f32(dw)
-                assert dw.numel() == c * k
-                part_m, part_s, part_w = f(nparts, k, k), f(nparts, k), f(nparts, c, k)
-                ms = torch.empty(k * k + k, dtype=torch.float64, device=dev)
-                _lib.call("nesie_pool_tail_wgrad", nb, k, c, p, ns, _ptr(z_prev), zbs, _ptr(coef_prev),
-                          _ptr(ent), _ptr(ab), _ptr(w), _ptr(part_m), _ptr(part_s), _ptr(part_w),
-                          _ptr(ms), _ptr(dw), st)
+        _launch("nesie_pool_tail_prepare", g, nb, c, m, ns, k, g, pooled, zstar, argmax, coef,
+                gamma, w, dgamma, dbeta, ab, ent, wcat, c0)
+        _launch("nesie_pool_tail_dgrad", g, nb, k, c, p, ns, z_prev, zbs, coef_prev, wcat, c0, ent,
+                da, k * p, part)
+        if dw is not None:
+            _check(dw); _f32(dw)
+            assert dw.numel() == c * k
+            part_m, part_s, part_w = f(nparts, k, k), f(nparts, k), f(nparts, c, k)
+            ms = torch.empty(k * k + k, dtype=torch.float64, device=dev)
+            _launch("nesie_pool_tail_wgrad", g, nb, k, c, p, ns, z_prev, zbs, coef_prev, ent, ab, w,
+                    part_m, part_s, part_w, ms, dw)
         return da, part
 
     def mlp_stat_finalize(self, part, count, gamma, beta, running_mean, running_var, momentum, eps,
@@ -1478,11 +1332,8 @@ class HipKernels(_BNPoolMixin):
             c, nparts, _ = part.shape
         else:
             nparts, c, _ = part.shape
-        opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-        with torch.cuda.device(coef.device):
-            _lib.call("nesie_mlp_stat_finalize", c, nparts, float(count), _ptr(part), opt(gamma),
-                      opt(beta), opt(running_mean), opt(running_var), float(momentum), float(eps),
-                      _ptr(coef), int(bool(channel_major)), _stream(coef))
+        _launch("nesie_mlp_stat_finalize", coef, c, nparts, float(count), part, gamma, beta,
+                running_mean, running_var, float(momentum), float(eps), coef, bool(channel_major))
 
     def bn_relu_backward(self, dy, x, y, gamma, beta, save_mean, save_invstd, fwd_coef, relu,
                          dx, dgamma, dbeta, row_bias=None, d_row_bias=None, group=None):
@@ -1506,13 +1357,9 @@ class HipKernels(_BNPoolMixin):
         elif row_bias is not None:
             assert d_row_bias is None  # per-channel bias before a batch norm: gradient is zero
         need = _lib.load().nesie_bn_workspace_bytes(b, c, p)
-        with torch.cuda.device(x.device):
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
-            opt = lambda t: 0 if t is None else _ptr(t)  # noqa: E731
-            _lib.call("nesie_bn_relu_backward", b, c, p, _ptr(dy), _ptr(x), opt(y), opt(gamma),
-                      opt(beta), opt(save_mean), opt(save_invstd), _ptr(fwd_coef),
-                      int(bool(relu)), _ptr(dx), opt(dgamma), opt(dbeta), opt(row_bias), group,
-                      opt(d_row_bias), _ptr(ws), need, _stream(x))
+        ws = _workspace(need, x.device)
+        _launch("nesie_bn_relu_backward", x, b, c, p, dy, x, y, gamma, beta, save_mean, save_invstd,
+                fwd_coef, bool(relu), dx, dgamma, dbeta, row_bias, group, d_row_bias, ws, need)
 
 
 def _row_bias_group(x, row_bias):

@@ -34,21 +34,121 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/ but not exported"
 
 
-def test_binding_covers_every_compute_entry_point():
-    compute = [n for n in declared_symbols()
-               if n not in ("nesie_abi_version", "nesie_last_error",
-                            "nesie_set_distance_form", "nesie_get_distance_form", "nesie_set_cu_count", "nesie_get_cu_count",
-                            "nesie_fps_workspace_bytes", "nesie_fps_leaves_index",
-                            "nesie_bn_workspace_bytes",
-                            "nesie_pw_supported", "nesie_pw_stat_slots", "nesie_pw_wgrad_supported", "nesie_pw_wgrad_tiled", "nesie_pool_tail_supported",
-                            "nesie_pw_wgrad_workspace_bytes", "nesie_pw_wgrad_pending", "nesie_k4_moments_bytes", "nesie_pw_wgrad_bn_backward_k4_slots", "nesie_pw_wgrad_bn_supported", "nesie_blend_conv_runs", "nesie_blend_conv_backward_workspace_bytes",
-                            "nesie_conv_wgrad_workspace_bytes", "nesie_mlp_stream_partials",
-                            "nesie_blend_conv_bn_workspace_bytes",
-                            "nesie_flat_adamw_workspace_bytes")]
-    assert sorted(compute) == sorted(_lib.SIGNATURES)
+def test_binding_is_derived_for_every_declared_function():
+    assert sorted(_lib.SIGNATURES) == declared_symbols()
     lib = _lib.load()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == list(argtypes), name
     assert lib.nesie_abi_version() >= 1
     assert isinstance(lib.nesie_last_error(), bytes)
+
+
+# The referee: prototypes transcribed by hand from include/*.h, one letter per parameter
+# (I int, F float, D double, L long long, Z size_t, P any pointer; the stream is a pointer).
+_CODES = {"I": ctypes.c_int, "F": ctypes.c_float, "D": ctypes.c_double, "L": ctypes.c_longlong,
+          "Z": ctypes.c_size_t, "P": ctypes.c_void_p}
+HAND_WRITTEN = {
+    # (int b, n, m, float min_radius, max_radius, int nsample, const float *new_xyz,
+    #  const void *fps_workspace, size_t workspace_bytes, int *idx, void *stream)
+    "nesie_ball_query_indexed": (ctypes.c_int, "IIIFFIPPZPP"),
+    # (int nb, ng, k, cout, long long p, x, long long x_bstride, w, long long w_gstride,
+    #  int w_rstride, w_cstride, in_coef, int in_relu, row_bias, int rb_group, bias, y,
+    #  long long y_bstride, stat_part, int pool_group, pool_min, float *pool_max_out, pool_min_out,
+    #  uint8_t *arg_max_out, arg_min_out, void *stream)
+    "nesie_pw_layer_forward": (ctypes.c_int, "IIIIL" "PLPL" "II" "PIPIPP" "LP" "II" "PPPP" "P"),
+    # (int channels, nslots, double count, part, z_coef, gamma, bnb, dgamma, dbeta, stream)
+    "nesie_pw_bnb_coef": (ctypes.c_int, "IID" "PPPPPP" "P"),
+    # (int b, k, t, c, cls, bbox, surface, side, iou_s, iou, quality, int detach_sigma,
+    #  const long long *obj_t, label, obj_w, box_w, bbox_t, centre_t, valid_w, config, loss,
+    #  s_cls, s_centre, s_surface, s_iou, s_iou_s, s_side_surf, s_side_iou, s_side_pred,
+    #  sem_pick, kstar, dmin, partial, ticket, stream)
+    "nesie_head_loss_forward_unsup": (ctypes.c_int, "IIII" "PPPPPPP" "I" "PPPPPPP" "PP" "PPPPPPPP"
+                                      "PPPPP" "P"),
+    # (int b, k, c, g, const long long *label, s_robj, s_angle, s_rot, s_sidej, d_robj, d_angle,
+    #  d_rot, d_side, stream)
+    "nesie_saqe_extra_loss_backward": (ctypes.c_int, "III" "PPPPPP" "PPPP" "P"),
+    "nesie_fps_workspace_bytes": (ctypes.c_size_t, "II"),           # size_t (int b, int n)
+    "nesie_mlp_stream_partials": (ctypes.c_longlong, "IL"),         # long long (int b, long long p)
+    "nesie_last_error": (ctypes.c_char_p, ""),                      # const char * (void)
+    "nesie_pw_wgrad_drop_deferred": (ctypes.c_int, ""),             # int (void)
+}
+
+
+def test_parser_agrees_with_prototypes_written_out_by_hand():
+    assert len(HAND_WRITTEN["nesie_pw_layer_forward"][1]) == 26
+    for name, (restype, codes) in HAND_WRITTEN.items():
+        got_restype, got_argtypes = _lib.SIGNATURES[name]
+        assert got_restype is restype, name
+        assert got_argtypes == [_CODES[c] for c in codes], name
+
+
+def test_parser_reads_every_spelling_the_headers_use():
+    protos = _lib.parse_prototypes("""
+        /* int nesie_in_a_comment(int a); */
+        // size_t nesie_in_a_line_comment(void);
+        #define NESIE_NOT_A_PROTOTYPE(x) nesie_macro(x)
+        typedef enum { NESIE_OK = 0 } nesie_status;
+        int nesie_all(int a, float b, double c, long long d, size_t e, const float *f,
+                      const long long *g, uint8_t *h, const void *i,
+                      void *stream);
+        size_t nesie_bytes(void);
+        long long nesie_count();
+        const char *nesie_text(void);
+    """)
+    c = ctypes
+    assert protos == {
+        "nesie_all": (c.c_int, [c.c_int, c.c_float, c.c_double, c.c_longlong, c.c_size_t]
+                      + [c.c_void_p] * 5),
+        "nesie_bytes": (c.c_size_t, []),
+        "nesie_count": (c.c_longlong, []),
+        "nesie_text": (c.c_char_p, []),
+    }
+
+
+def test_parser_refuses_a_type_it_does_not_know():
+    import pytest
+    with pytest.raises(TypeError, match="nesie_narrow.*short n"):
+        _lib.parse_prototypes("int nesie_ok(int a);\nint nesie_narrow(int a, short n, void *stream);")
+    with pytest.raises(TypeError, match="nesie_wide.*unsigned long"):
+        _lib.parse_prototypes("int nesie_wide(unsigned long n);")
+    with pytest.raises(TypeError, match="nesie_ret.*unsigned"):
+        _lib.parse_prototypes("unsigned nesie_ret(int a);")
+
+
+def test_call_is_for_functions_that_return_a_status():
+    import pytest
+    for name in ("nesie_fps_workspace_bytes", "nesie_mlp_stream_partials", "nesie_last_error"):
+        with pytest.raises(TypeError, match=name):
+            _lib.call(name)
+
+
+def test_launch_helper_refuses_a_call_the_header_does_not_describe(monkeypatch):
+    """Every refusal comes before the library is reached (so none of this needs a GPU)."""
+    import pytest
+    import torch
+    from nesie_amd import kernels
+
+    def no_call(name, *args):
+        raise AssertionError(f"{name} reached the library")
+    monkeypatch.setattr(_lib, "call", no_call)
+    x, i = torch.zeros(4), torch.zeros(4, dtype=torch.int32)
+    # int nesie_gather_rows3(int b, int n, int m, const float *xyz, const int *sample, float *out,
+    #                        void *stream)
+    with pytest.raises(RuntimeError, match="need HIP device tensors.*no CPU path"):
+        kernels._launch("nesie_gather_rows3", x, 1, 4, 4, x, i, x)
+    with pytest.raises(TypeError, match="nesie_gather_rows3"):
+        kernels._launch("nesie_gather_rows3", x, 1, 4, 4, x, i)          # one too few
+    with pytest.raises(TypeError, match="nesie_gather_rows3"):
+        kernels._launch("nesie_gather_rows3", x, 1, 4, 4, x, i, x, x)    # one too many
+    with pytest.raises(TypeError, match="nesie_gather_rows3: argument 2 is a c_int"):
+        kernels._launch("nesie_gather_rows3", x, 1, 4, i, x, i, x)       # a tensor for int m
+    with pytest.raises(TypeError, match="nesie_gather_rows3: argument 3 is a pointer"):
+        kernels._launch("nesie_gather_rows3", x, 1, 4, 4, 0.5, i, x)     # a float for xyz
+    # int nesie_ball_query_wrapper(int b, int n, int m, float min_radius, float max_radius, ...)
+    with pytest.raises(TypeError, match="nesie_ball_query_wrapper: argument 3 is a c_float"):
+        kernels._launch("nesie_ball_query_wrapper", x, 1, 4, 4, None, 1.0, 2, x, x, i)
 
 
 def test_invalid_arguments_return_a_status_not_a_crash():
