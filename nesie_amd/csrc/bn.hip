@@ -612,27 +612,6 @@ extern "C" int nesie_bn_relu_backward_apply(int b, int c, long long p, const flo
   return check_launch(W);
 }
 
-// For producers that compute the (sum, sum of squares) partials themselves
-// (partial[(c * nslice + i) * 2 + {0,1}], unshifted): interpolate.hip's blend + norm kernels.
-namespace nesie {
-int launch_bn_finalize(int c, int nslice, double count, const float *partial,
-                       const float *gamma, const float *beta, float *running_mean,
-                       float *running_var, float momentum, float eps, float *save_mean,
-                       float *save_invstd, float *coef, hipStream_t s) {
-  const BnFwdFin fin{nslice, count, nullptr, 0, nullptr, 1, partial, gamma, beta, running_mean,
-                     running_var, momentum, eps, save_mean, save_invstd, coef};
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(64), 0, s, fin, c);
-  return check_launch("bn_finalize");
-}
-int launch_bn_bwd_finalize(int c, int nslice, double count, const float *partial,
-                           const float *gamma, const float *save_invstd, float *dgamma,
-                           float *dbeta, float *coef, hipStream_t s) {
-  const BnBwdFin fin{nslice, count, partial, gamma, save_invstd, dgamma, dbeta, 1};
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(64), 0, s, fin, c, coef);
-  return check_launch("bn_bwd_finalize");
-}
-}  // namespace nesie
-
 static int bn_pool_dims(const char *W, int m, int ns) {
   if (m <= 0 || ns < 4 || ns > 64 || (ns & (ns - 1))) {
     set_error("%s: m %d, nsample %d (needs a power of two in 4..64)", W, m, ns);

@@ -556,40 +556,6 @@ class HipKernels:
         if part is not None:      # (d_wx arrives zero-filled or empty from its caller: the sum overwrites it)
             torch.sum(part, 0, out=d_wx)
 
-    def blend_conv_bn_forward(self, table, idx, weight, rel, wx, gamma, beta, running_mean,
-                              running_var, momentum, eps, out, save_mean, save_invstd, fwd_coef,
-                              segs, seg_len):
-        """out (B, segs, c, n/segs) = relu(bn(blend conv)); table (B, M, segs*c)."""
-        _check(table, idx, weight, rel, wx, out, save_mean, save_invstd, fwd_coef)
-        _f32(table, weight, rel, wx, out); _i32(idx)
-        b, m, pitch = table.shape
-        n, c = idx.shape[1], pitch // segs
-        assert tuple(out.shape) == (b, segs, c, n // segs) and tuple(wx.shape) == (segs, c, 3)
-        lib = _lib.load()
-        need = lib.nesie_blend_conv_bn_workspace_bytes(b, c, n, segs)
-        ws = _workspace(need, table.device)
-        _launch("nesie_blend_conv_bn_forward", table, b, c, m, n, table, pitch, c, idx, weight, rel,
-                wx, gamma, beta, running_mean, running_var, float(momentum), float(eps), out,
-                save_mean, save_invstd, fwd_coef, ws, need, segs, seg_len)
-
-    def blend_conv_bn_backward(self, dy, table, idx, weight, rel, wx, gamma, save_invstd,
-                               fwd_coef, d_table, d_wx, dgamma, dbeta, segs, seg_len):
-        """d_table (zeroed) += ..., d_wx (segs, c, 3) += ..., dgamma / dbeta [segs*c] written."""
-        _check(dy, table, idx, weight, rel, wx, d_table, d_wx, dgamma, dbeta)
-        _f32(dy, table, d_table); _i32(idx)
-        b, m, pitch = table.shape
-        n, c = idx.shape[1], pitch // segs
-        assert tuple(dy.shape) == (b, segs, c, n // segs) and d_table.shape == table.shape
-        lib = _lib.load()
-        need = lib.nesie_blend_conv_bn_workspace_bytes(b, c, n, segs)
-        runs = lib.nesie_blend_conv_runs(n, segs)
-        ws = _workspace(need, dy.device)
-        part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
-        _launch("nesie_blend_conv_bn_backward", dy, b, c, m, n, dy, table, pitch, c, idx, weight,
-                rel, wx, gamma, save_invstd, fwd_coef, d_table, part, dgamma, dbeta, ws, need, segs,
-                seg_len)
-        d_wx += part.sum(0)
-
     def three_interpolate_grad_wrapper(self, b, c, n, m, grad_out, idx, weight,
                                        grad_points):
         _check(grad_out, idx, weight, grad_points); _f32(grad_out, weight, grad_points)

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from .. import grad_slots
 from ..kernels import backend_for
-from ..mmdet3d_ops import blend_conv, blend_conv_bn, three_interpolate_segmented, three_nn
+from ..mmdet3d_ops import blend_conv, three_interpolate_segmented, three_nn
 from ..mmdet3d_ops.pool import group_max_pool, group_max_pool_shared
 from ..mmdet3d_ops.norm import FusedBNReLU1d, FusedBNReLU2d
 from ..mmdet3d_ops.pointnet_modules import PointwiseConv1d, PointwiseConv2d, pointwise_conv
@@ -85,12 +85,13 @@ class DeferredBlendConv:
 
 
 def _resolve_c0(nets, c0, c0_stats):
-    """A deferred first-conv output stays deferred only for the fused MiniPointNet path."""
+    """-> (c0, c0_stats, fused?).  A deferred first-conv output stays deferred only for the fused
+    MiniPointNet path; any other consumer gets the tensor and its statistics partials."""
     if isinstance(c0, DeferredBlendConv):
         if fused_mini_ok(nets, c0, None):
-            return c0, None
-        return c0.materialize()
-    return c0, c0_stats
+            return c0, None, True
+        c0, c0_stats = c0.materialize()
+    return c0, c0_stats, fused_mini_ok(nets, c0, c0_stats)
 
 
 class MiniPointNet(nn.Module):
@@ -106,10 +107,10 @@ class MiniPointNet(nn.Module):
             PointwiseConv2d(hide_dim, hide_dim, 1, bias=False), FusedBNReLU2d(hide_dim),
             nn.Identity(), PointwiseConv2d(hide_dim, feature_dim, 1))
 
-    def forward(self, points=None, conv0_out=None, a0=None, c0_stats=None):
-        """``points`` (B,C,K,G) grid features, or ``conv0_out`` (B,H,K,G) = the first conv
-        already applied through the blend (SidePooling.first_conv_through_blend), or ``a0`` =
-        that followed by the first norm + ReLU as well (``with_norm=True`` there).
+    def forward(self, points=None, conv0_out=None, c0_stats=None):
+        """``points`` (B,C,K,G) grid features, or ``conv0_out`` = the first conv already applied
+        through the blend: (B,H,K,G), with ``c0_stats`` = its statistics partials if its producer
+        left any, or the ``DeferredBlendConv`` of SidePooling.first_conv_through_blend.
 
         Same function as the reference's
             f = first_conv(x); g = max_G f; y = second_conv(cat[g expanded, f]); out = max_G y
@@ -121,15 +122,15 @@ class MiniPointNet(nn.Module):
         Differences from the concatenated form are summation-order rounding only."""
         conv0, bn0, _, conv3 = self.first_conv
         sconv0, sbn0, _, sconv3 = self.second_conv
-        if isinstance(conv0_out, DeferredBlendConv):      # (one net: S = 1)
-            conv0_out, c0_stats = _resolve_c0([self], conv0_out, c0_stats)
-            if isinstance(conv0_out, DeferredBlendConv):
-                return fused_mini_pointnets([self], conv0_out, c0_stats).squeeze(1)
-            conv0_out = conv0_out.squeeze(1)
-        if a0 is None and conv0_out is not None and fused_mini_ok([self], conv0_out.unsqueeze(1), c0_stats):
-            return fused_mini_pointnets([self], conv0_out.unsqueeze(1), c0_stats).squeeze(1)
-        if a0 is None:   # c0_stats: (sum, sum^2) partials of conv0_out left by its producer
-            a0 = bn0(conv0(points)) if conv0_out is None else bn0(conv0_out, pre_partial=c0_stats)
+        if conv0_out is None:
+            a0 = bn0(conv0(points))
+        else:                                             # (one net: S = 1)
+            if not isinstance(conv0_out, DeferredBlendConv):
+                conv0_out = conv0_out.unsqueeze(1)
+            c0, c0_stats, fused = _resolve_c0([self], conv0_out, c0_stats)
+            if fused:
+                return fused_mini_pointnets([self], c0, c0_stats).squeeze(1)
+            a0 = bn0(c0.squeeze(1), pre_partial=c0_stats)
         c = pointwise_conv(a0, conv3.weight)                           # f without its bias
         g, c = group_max_pool_shared(c)                                # (B, H, K): max_G f - b
         half = conv3.out_channels
@@ -196,23 +197,21 @@ def _stackable_bn(layers):
                for l in layers)
 
 
-def grouped_mini_pointnets(nets, c0, normed=False, c0_stats=None):
+def grouped_mini_pointnets(nets, c0, c0_stats=None):
     """S structurally identical MiniPointNets on S inputs at once: ``c0`` (B, S, H, K, G) =
-    the outputs of their first convs (``normed``: already through the first norm + ReLU) ->
-    (B, S, F, K).  Same function as calling
+    the outputs of their first convs (a tensor, or a ``DeferredBlendConv``) -> (B, S, F, K).
+    Same function as calling
     ``net(conv0_out=c0[:, i])`` for each net (see MiniPointNet.forward for the algebra); every
     1x1 conv is one broadcast batched GEMM over the stacked weights (48 instead of 8 matrices
     per launch at B = 8) and every norm layer one stacked BatchNorm."""
-    if not normed:
-        c0, c0_stats = _resolve_c0(nets, c0, c0_stats)
-    B, S, H, K, G = c0.shape
-    if not normed and fused_mini_ok(nets, c0, c0_stats):
+    c0, c0_stats, fused = _resolve_c0(nets, c0, c0_stats)
+    if fused:
         return fused_mini_pointnets(nets, c0, c0_stats)
+    B, S, H, K, G = c0.shape
     f, sc = [n.first_conv for n in nets], [n.second_conv for n in nets]
     stack = lambda ws: torch.stack([w.flatten(1) for w in ws]).unsqueeze(0)  # noqa: E731
-    a0 = c0.reshape(B, S, H, K * G) if normed else \
-        _stacked_bn([x[1] for x in f], c0.reshape(B, S * H, K, G),
-                    pre_partial=c0_stats).view(B, S, H, K * G)
+    a0 = _stacked_bn([x[1] for x in f], c0.reshape(B, S * H, K, G),
+                     pre_partial=c0_stats).view(B, S, H, K * G)
     c = torch.matmul(stack([x[3].weight for x in f]), a0)               # (B,S,half,K*G)
     half = c.shape[2]
     g, c5 = group_max_pool_shared(c.view(B, S, half, K, G))              # (B,S,half,K)
@@ -445,6 +444,11 @@ def _score_head(in_ch, out_ch):
 
 
 class SidePooling(nn.Module):
+    # what the SAQE variant (quality_estimation.QualityEstimation) sets differently
+    grid_size = 4        # grid points per box edge
+    hide_dim = 256       # width of the MiniPointNets
+    plane_axes = None    # per face, the box-frame axis of its +-10 % plane offsets (SAQE)
+
     def __init__(self, num_class, num_heading_bin, num_size_cluster, mean_size_arr_path,
                  num_proposal, sampling, seed_feat_dim=256, query_feats='seed',
                  iou_class_depend=True):
@@ -460,7 +464,7 @@ class SidePooling(nn.Module):
         self.query_feats = query_feats
         self.iou_class_depend = iou_class_depend
         self.reg_topk = 4
-        self.grid_size = g = 4
+        g = self.grid_size
         self.left_mask = [i // g * g * g + i % g for i in range(g * g)]
         self.right_mask = [i // g * g * g + i % g + g * (g - 1) for i in range(g * g)]
         # the six face selections of grid_for_side as ONE device-resident index (graph-safe)
@@ -469,16 +473,33 @@ class SidePooling(nn.Module):
                     + self.left_mask + self.right_mask)
         self.register_buffer('_face_idx', torch.tensor(face_idx, dtype=torch.long),
                              persistent=False)
-        self._register_grid_tables(face_idx)
+        plane = None
+        if self.plane_axes is not None:
+            plane = torch.zeros(6, 3)
+            for f, a in enumerate(self.plane_axes):
+                plane[f, a] = 0.1
+            self.register_buffer('_plane_axis', plane, persistent=False)
+        self._register_grid_tables(face_idx, plane)
         self.iou_size = num_class if iou_class_depend else 1
         before, head = [], []
         for _ in range(6):
-            before.append(MiniPointNet(seed_feat_dim + 3, 128))
-            head.append(_score_head(128 + 33 + 4 + 1, self.iou_size))
-        before.append(MiniPointNet(seed_feat_dim + 3, 128))
-        head.append(_score_head(128, self.iou_size))
+            before.append(MiniPointNet(seed_feat_dim + 3, 128, hide_dim=self.hide_dim))
+            head.append(self._side_head(128 + 33 + 4 + 1))
+        self._add_final(before, head)
         self.mlps_before = nn.ModuleList(before)
         self.mlps_head = nn.ModuleList(head)
+
+    def _side_head(self, in_ch):
+        """Score head of one face over [pooled grid features, side-bin statistics]."""
+        return _score_head(in_ch, self.iou_size)
+
+    def _add_final(self, before, head):
+        """What follows the six face pairs: the box-grid MiniPointNet and the IoU head.  An
+        override appends to either list, or to one only.  The modules are built here, after the
+        six pairs and in the order before-then-head: that order fixes the parameter order of the
+        state and what each initialisation draws from the random generator."""
+        before.append(MiniPointNet(self.seed_feat_dim + 3, 128, hide_dim=self.hide_dim))
+        head.append(_score_head(128, self.iou_size))
 
     def stacked_parameter_groups(self):
         """Lists of parameters the step uses STACKED: tensor kind by tensor kind, the six side
@@ -492,12 +513,6 @@ class SidePooling(nn.Module):
                 groups += [list(kind) for kind in zip(*per)
                            if all(t.shape == kind[0].shape for t in kind)]
         return groups
-
-    # BlendConvBN (first conv AND its norm + ReLU by recomputation, the conv output never
-    # stored) is exact and saves 1.3 GB of activations, but measured break-even on MI355X: the
-    # forward gains 0.23 ms, the backward loses 0.3 ms to the recomputed row gathers at the two
-    # waves per SIMD its LDS tile allows.  Off; flip to trade time for memory.
-    fuse_first_norm = False
 
     def _register_grid_tables(self, face_idx, plane=None):
         """Box-frame multipliers of the grid points of one proposal, in the order the grids are
@@ -578,44 +593,22 @@ class SidePooling(nn.Module):
         return idx, weight, relative_grid.contiguous()
 
     def first_conv_through_blend(self, nets, origin_xyz, origin_features, whole_grid, center,
-                                 taps=None, with_norm=False, defer=False):
+                                 taps=None):
         """Outputs of ``net.first_conv[0]`` for the S = len(nets) MiniPointNets that read the
-        S consecutive point groups of every proposal: ((B,S,H,K,G), normed?, statistics partials
-        of the output for the first norm layer or None), evaluated as
+        S consecutive point groups of every proposal, (B,S,H,K,G), as a ``DeferredBlendConv``:
+        evaluated by its consumer (BlendMiniHeadFn, or ``materialize()`` for any other) as
         W_xyz . rel + blend(W_f . F) (mmdet3d_ops.BlendConv) instead of
-        conv(cat[rel, blend(F)]) -- the conv runs over the N seeds, not the K*S*G grid points.
-        ``defer``: return the operands as a ``DeferredBlendConv`` instead of the tensor."""
-        B, K = center.shape[:2]
+        conv(cat[rel, blend(F)]) -- the conv runs over the N seeds, not the K*S*G grid points."""
+        K = center.shape[1]
         segs = len(nets)
         idx, weight, rel = taps if taps is not None \
             else self._blend_taps(origin_xyz, whole_grid, center)
         G = idx.shape[1] // (K * segs)
         from ..mmdet3d_ops import fused_mlp
         w = fused_mlp.stack_groups([[net.first_conv[0].weight.flatten(1) for net in nets]])[0]   # (S, H, 3+C)
-        H = w.shape[1]
         w_xyz, w_feat = fused_mlp.SplitXyzFeat.apply(w)       # (S, H, 3) contiguous, (S*H, C) view
         table = _TableProduct.apply(origin_features, w_feat)  # (B,N,S*H)
-        bns = [net.first_conv[1] for net in nets]
-        if with_norm and _stackable_bn(bns) and H % 64 == 0 and H <= 256 and (K * G) % 64 == 0 \
-                and origin_features.dtype == torch.float32:
-            # ... and the norm + ReLU behind it, the conv output never stored (BlendConvBN)
-            from ..mmdet3d_ops import norm as _norm
-            rm = torch.cat([l.running_mean for l in bns])
-            rv = torch.cat([l.running_var for l in bns])
-            out = blend_conv_bn(table, w_xyz, torch.cat([l.weight for l in bns]),
-                                torch.cat([l.bias for l in bns]), idx, weight, rel, rm, rv,
-                                bns[0].momentum, bns[0].eps, segs, G)
-            with torch.no_grad():
-                torch._foreach_copy_([l.running_mean for l in bns], list(rm.split(H)))
-                torch._foreach_copy_([l.running_var for l in bns], list(rv.split(H)))
-                for l in bns:
-                    _norm.count_batch(l.num_batches_tracked)
-            return out.view(B, segs, H, K, G), True, None
-        if defer:   # evaluated by its consumer (BlendMiniHeadFn, or materialize() for any other)
-            return DeferredBlendConv(table, w_xyz, idx, weight, rel, segs, G, K), False, None
-        # (B, S, H, K*G) and the (sum, sum^2) partials of it for the first norm layer
-        out, stats = blend_conv(table, w_xyz, idx, weight, rel, segs, G, True)
-        return out.view(B, segs, H, K, G), False, (stats if stats.numel() else None)
+        return DeferredBlendConv(table, w_xyz, idx, weight, rel, segs, G, K)
 
     def grid_features(self, origin_xyz, origin_features, whole_grid, center, segs=1):
         """(B,N,3),(B,N,C),(B,K*S*G,3),(B,K,3) -> (B,S,3+C,K,G)  (:183-243).
@@ -646,53 +639,57 @@ class SidePooling(nn.Module):
                           prob.var(dim=2, keepdim=True)], dim=2)
         return stat.permute(1, 0, 2, 3).repeat(1, 1, 1, copies)   # copies = 1: no jittered half
 
-    def forward(self, center, size, heading, end_points, prefix=''):
+    def _side_input(self, center, size, heading, end_points, prefix):
+        """-> x (B, 6, 166, 2K): per face, the MiniPointNet-pooled grid features on top of the
+        side-bin statistics (side_pooling_module.py:296-313); and the forward arguments of the
+        box-grid MiniPointNet ``mlps_before[6]`` (None in a variant without one).  Both grid
+        sets are sampled here, before any net runs: the launch order the step was tuned with."""
         B, K = size.shape[:2]
         origin_xyz, origin_features = self.extract_features(end_points)
+        nets, box_net = list(self.mlps_before[:6]), self.mlps_before[6:7]
+        box_in = None
         fused = backend_for(origin_xyz).name == 'hip'
-        side_nets = list(self.mlps_before[:6])
-        if fused:   # grids + taps in one launch each, first convs (+ norm) through the blend;
-            #         the literal form below stays the CPU checker's
-            side_c0, side_normed, side_stats = self.first_conv_through_blend(
-                side_nets, origin_xyz, origin_features, None, center,
-                taps=self.fused_taps(origin_xyz, center, size, heading, 'side'),
-                with_norm=self.fuse_first_norm, defer=True)
-            bbox_c0, bbox_normed, bbox_stats = self.first_conv_through_blend(
-                self.mlps_before[6:7], origin_xyz, origin_features, None, center,
-                taps=self.fused_taps(origin_xyz, center, size, heading, 'box'),
-                with_norm=self.fuse_first_norm, defer=True)
-            if not isinstance(bbox_c0, DeferredBlendConv):
-                bbox_c0 = bbox_c0.squeeze(1)   # (a view: indexing [:, 0] costs a zero-filled gradient)
+        if fused:
+            # grid + taps in one launch each, first convs through the blend; the literal form
+            # below stays the CPU checker's
+            c0 = self.first_conv_through_blend(
+                nets, origin_xyz, origin_features, None, center,
+                taps=self.fused_taps(origin_xyz, center, size, heading, 'side'))
+            if len(box_net):
+                box_in = dict(conv0_out=self.first_conv_through_blend(
+                    box_net, origin_xyz, origin_features, None, center,
+                    taps=self.fused_taps(origin_xyz, center, size, heading, 'box')))
         else:
             whole_grid = self.generate_grid(size)
             side_grid = self.grid_for_side(whole_grid, center, heading).view(B, -1, 3).contiguous()
-            bbox_grid = self.grid_for_bbox(whole_grid, center, heading).view(B, -1, 3).contiguous()
             side_feats = self.grid_features(origin_xyz, origin_features, side_grid, center, segs=6)
-            bbox_feats = self.grid_features(origin_xyz, origin_features, bbox_grid, center)[:, 0]
+            if len(box_net):
+                bbox_grid = self.grid_for_bbox(whole_grid, center, heading).view(B, -1, 3) \
+                    .contiguous()
+                box_in = dict(points=self.grid_features(origin_xyz, origin_features, bbox_grid,
+                                                        center)[:, 0])
         dist_feature = self.dist_feature(end_points, prefix,
                                          copies=K // end_points[f'{prefix}bbox_probs'].shape[-1])
-        if fused and mini_pointnets_groupable(side_nets, side_c0):
-            pooled = grouped_mini_pointnets(side_nets, side_c0, normed=side_normed,
-                                            c0_stats=side_stats)               # (B,6,128,2K)
-        elif fused:
-            if isinstance(side_c0, DeferredBlendConv):
-                side_c0, side_stats = side_c0.materialize()
-            key = 'a0' if side_normed else 'conv0_out'
-            pooled = torch.stack([side_nets[i](**{key: side_c0[:, i]}) for i in range(6)], 1)
+        if fused and mini_pointnets_groupable(nets, c0):
+            pooled = grouped_mini_pointnets(nets, c0)                              # (B,6,128,2K)
+        elif fused:   # net by net, the first norm of each computing its own statistics
+            c0 = c0.materialize()[0]
+            pooled = torch.stack([nets[i](conv0_out=c0[:, i]) for i in range(6)], 1)
         else:
-            pooled = torch.stack([side_nets[i](side_feats[:, i]) for i in range(6)], 1)
+            pooled = torch.stack([nets[i](side_feats[:, i]) for i in range(6)], 1)
+        return torch.cat([pooled, dist_feature.transpose(0, 1)], dim=2), box_in
+
+    def _side_scores(self, x):
+        """x (B, 6, 166, 2K) -> (6, B, C, 2K), one score head per face (:314-321)."""
         heads = list(self.mlps_head[:6])
-        x = torch.cat([pooled, dist_feature.transpose(0, 1)], dim=2)      # (B,6,166,2K)
         if heads_batchable(heads, x[:, 0]):
-            side_scores = batched_heads(heads, x).transpose(0, 1).contiguous()
-        else:
-            side_scores = torch.stack([self.mlps_head[i](x[:, i]) for i in range(6)], 0)
-        end_points[f'{prefix}side_scores'] = side_scores
-        if fused:
-            bbox_feats = self.mlps_before[6](**{'a0' if bbox_normed else 'conv0_out': bbox_c0},
-                                             c0_stats=bbox_stats)
-        else:
-            bbox_feats = self.mlps_before[6](bbox_feats)
+            return batched_heads(heads, x).transpose(0, 1).contiguous()
+        return torch.stack([heads[i](x[:, i]) for i in range(6)], 0)
+
+    def forward(self, center, size, heading, end_points, prefix=''):
+        x, box_in = self._side_input(center, size, heading, end_points, prefix)
+        end_points[f'{prefix}side_scores'] = self._side_scores(x)
+        bbox_feats = self.mlps_before[6](**box_in)
         if heads_batchable([self.mlps_head[6]], bbox_feats):     # (one head: the same fused chain)
             iou = batched_heads([self.mlps_head[6]], bbox_feats.unsqueeze(1)).squeeze(1)
         else:
