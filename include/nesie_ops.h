@@ -101,6 +101,24 @@ int nesie_ball_query_indexed(int b, int n, int m, float min_radius, float max_ra
                              int nsample, const float *new_xyz, const void *fps_workspace,
                              size_t workspace_bytes, int *idx, void *stream);
 
+/* mmdet3d/ops/knn/src/knn.cpp  knn_wrapper
+ * (b, n, m, nsample, xyz[B,N,3], new_xyz[B,M,3], idx[B,M,nsample], dist2[B,M,nsample]).
+ * For every centre: the nsample points of the same scene with the smallest squared distance, the
+ * distance taken in the process-wide form above (fp32, left to right, no contraction by default),
+ * written in ascending order of the pair (distance, point index); dist2 receives the fp32
+ * distances.  With n < nsample the remaining slots hold index 0 and distance 1e10f, the state the
+ * reference's heap starts from (knn_cuda.cu:74-77); n == 0 fills both rows with that padding.
+ * The reference selects with a binary heap and heap-sorts: where a centre's distances are distinct
+ * that is the sorted k smallest, exactly this rule; where distances tie, its index order inside a
+ * group of equal distances follows the heap's history, here it is the point index.  The dist2 rows
+ * are equal in both cases.  (The reference's heap also never admits a point at d2 >= 1e10; here
+ * such a point is a point like any other.)
+ * nsample 1 .. 128 (the reference's arrays hold 100): nsample <= 0 or a negative size is
+ * NESIE_ERR_INVALID_ARG, nsample > 128 NESIE_ERR_UNSUPPORTED; b, m or n == 0 succeeds without a
+ * kernel launch. */
+int nesie_knn_wrapper(int b, int n, int m, int nsample, const float *xyz,
+                      const float *new_xyz, int *idx, float *dist2, void *stream);
+
 /* mmdet3d/ops/group_points/src/group_points.cpp:31-45  forward
  * (b, c, n, npoints, nsample, points[B,C,N], idx[B,M,ns], out[B,C,M,ns]). */
 int nesie_group_points_forward(int b, int c, int n, int npoints, int nsample,

@@ -179,6 +179,14 @@ class HipKernels:
         _launch("nesie_ball_query_wrapper", xyz, b, n, m, float(min_radius), float(max_radius),
                 nsample, new_xyz, xyz, idx)
 
+    def knn_wrapper(self, b, n, m, nsample, xyz, new_xyz, idx, dist2):
+        """idx, dist2 (B, M, nsample) <- the nsample nearest points of every centre, ascending in
+        (squared distance, point index) (nesie_knn_wrapper)."""
+        _check(xyz, new_xyz, idx, dist2); _f32(xyz, new_xyz, dist2); _i32(idx)
+        assert xyz.numel() == b * n * 3 and new_xyz.numel() == b * m * 3
+        assert idx.numel() == b * m * nsample and dist2.numel() == b * m * nsample
+        _launch("nesie_knn_wrapper", xyz, b, n, m, nsample, xyz, new_xyz, idx, dist2)
+
     def group_points_forward(self, b, c, n, npoints, nsample, points, idx, out):
         _check(points, idx, out); _f32(points, out); _i32(idx)
         assert points.numel() == b * c * n and idx.numel() == b * npoints * nsample

@@ -1,6 +1,6 @@
 """Host-side mirror of ``mmdet3d.ops`` for the VoteNet/Nesie hot path
 (reference mmdet3d/ops/__init__.py:5-41).  Hot-path names are real; the rest of
-the reference's ``__all__`` (voxel / spconv / paconv / knn / iou3d / roi-aware
+the reference's ``__all__`` (voxel / spconv / paconv / iou3d / roi-aware
 pooling ...) resolves to stubs that raise on use, so ``from mmdet3d.ops import X``
 style code keeps importing ("import-time requirement").
 """
@@ -13,6 +13,7 @@ from .interpolate import blend_conv, three_interpolate, three_interpolate_segmen
 from .pointnet_modules import (ConvModule, PointFPModule, PointSAModule, PointSAModuleMSG,
                                PointwiseConv1d, PointwiseConv2d, build_sa_module,
                                pointwise_conv)
+from .knn import knn
 from .iou3d import batched_nms_bev, boxes_iou_bev, boxes_overlap_bev, nms_gpu, nms_normal_gpu
 from .roiaware_pool3d import points_in_boxes_batch, points_in_boxes_count
 from .rotated_iou import cal_iou_3d, sort_v
@@ -23,7 +24,7 @@ _HOT = [
     'GroupAll', 'QueryAndGroup', 'PointSAModule', 'PointSAModuleMSG', 'PointFPModule',
     'points_in_boxes_batch', 'Points_Sampler', 'build_sa_module', 'cal_iou_3d', 'sort_v',
     'ConvModule', 'boxes_overlap_bev', 'points_in_boxes_count',
-    'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu',
+    'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu', 'knn',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
@@ -31,7 +32,7 @@ _OUT_OF_SCOPE = [
     'batched_nms', 'Voxelization', 'voxelization', 'dynamic_scatter', 'DynamicScatter',
     'sigmoid_focal_loss', 'SigmoidFocalLoss', 'SparseBasicBlock', 'SparseBottleneck',
     'RoIAwarePool3d', 'points_in_boxes_gpu', 'points_in_boxes_cpu',
-    'make_sparse_convmodule', 'knn', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
+    'make_sparse_convmodule', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
     'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule', 'PAConvCUDASAModuleMSG',
     'cal_giou_3d',
 ]

@@ -310,6 +310,14 @@ class SAStackFn(Function):
         return (dx, None, None) + tuple(grads)
 
 
+def _pooled_tail_whole(cin, cout):
+    """True when a pooled last layer cin -> cout is a whole number of row tiles: the pooling
+    epilogues of the layer kernel are built for whole row tiles only (pwconv.hip pw_geometry: 64
+    rows for <= 64 channels over <= 128 inputs, else 128; pwconv_fwd.h GOW).  Any other width (a
+    32-channel level, say) goes module by module."""
+    return cout % 128 == 0 or (cout == 64 and cin <= 128)
+
+
 def sa_stack_supported(backend, x, layers):
     """True when ``SAStackFn`` serves this shared MLP: native training BatchNorm behind bias-free
     1x1 convs, fp32, nsample in {16, 32, 64}, every layer inside the built tiles."""
@@ -336,6 +344,8 @@ def sa_stack_supported(backend, x, layers):
             return False
         if i > 0 and not backend.pw_supported(cout, cin, P):   # input-gradient product
             return False
+        if i == len(layers) - 1 and not _pooled_tail_whole(cin, cout):
+            return False
         cin = cout
     return True
 
@@ -356,6 +366,8 @@ def sa_stack_eval_supported(backend, x, layers):
                 and not norm.training and norm.track_running_stats and norm.running_mean is not None
                 and layer.conv.in_channels == cin
                 and backend.pw_supported(cin, layer.conv.out_channels, M * ns)):
+            return False
+        if layer is layers[-1] and not _pooled_tail_whole(cin, layer.conv.out_channels):
             return False
         cin = layer.conv.out_channels
     return True

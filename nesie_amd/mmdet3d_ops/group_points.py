@@ -8,6 +8,7 @@ from torch.autograd import Function
 
 from ..kernels import backend_for
 from .ball_query import ball_query
+from .knn import knn
 
 
 class GroupingOperation(Function):
@@ -155,6 +156,8 @@ SAMPLE_GROUP_FUSED = True
 
 def sample_query_group_supported(points_xyz, features, grouper):
     """True when ``SampleQueryGroupCat`` serves a grouper over differentiable coordinates."""
+    if grouper.max_radius is None or grouper.uniform_sample:     # the node is a plain ball query's only
+        return False
     backend = backend_for(points_xyz)
     return (SAMPLE_GROUP_FUSED and getattr(backend, 'name', '') == 'hip' and features is not None
             and grouper.use_xyz
@@ -164,10 +167,36 @@ def sample_query_group_supported(points_xyz, features, grouper):
             and (points_xyz.requires_grad or features.requires_grad))
 
 
+def uniform_resample(idx, generator=None):
+    """idx (..., sample_num) integer -> (idx, unique_cnt): every row's distinct indices in ascending
+    order first, then ``sample_num - count`` draws, uniform with replacement, from those distinct
+    indices; unique_cnt (...) float32 = count (reference :84-96, which loops over the rows in
+    Python with ``torch.unique`` and ``torch.randint``).  Here: sort, first-occurrence mask, stable
+    compaction, one ``torch.randint`` for all rows reduced modulo the row's count (its range of
+    2**62 leaves a bias below 2**-55).  Pure torch, any device.  The draws are not the reference's
+    random stream; every other property of a row is."""
+    ns = idx.shape[-1]
+    ordered = torch.sort(idx.long(), dim=-1)[0]
+    first = torch.ones_like(ordered, dtype=torch.bool)
+    first[..., 1:] = ordered[..., 1:] != ordered[..., :-1]
+    count = first.sum(-1, keepdim=True)
+    # first occurrences to the front, in their (ascending) order
+    front = torch.sort((~first).to(torch.uint8), dim=-1, stable=True)[1]
+    distinct = torch.gather(ordered, -1, front)
+    draw_device = idx.device if generator is None else generator.device
+    draws = torch.randint(0, 1 << 62, ordered.shape, generator=generator, device=draw_device)
+    slot = torch.arange(ns, device=idx.device).expand_as(ordered)
+    take = torch.where(slot < count, slot, draws.to(idx.device) % count)
+    out = torch.gather(distinct, -1, take).to(idx.dtype).contiguous()
+    return out, count.squeeze(-1).to(torch.float32)
+
+
 class QueryAndGroup(nn.Module):
     """ball query -> group xyz -> minus centre (-> / radius) -> group features ->
-    concat [xyz(3), features(C)]  (reference :64-128).  kNN grouping
-    (``max_radius is None``) and ``uniform_sample`` are outside the hot path."""
+    concat [xyz(3), features(C)]  (reference :64-128).  ``max_radius=None`` groups the
+    ``sample_num`` nearest neighbours instead (:75-79; ``min_radius`` is then ignored);
+    ``uniform_sample`` replaces every row's repeats by uniform draws from its distinct indices
+    (``uniform_resample``; set the attribute ``generator`` for a reproducible stream)."""
 
     def __init__(self, max_radius, sample_num, min_radius=0, use_xyz=True,
                  return_grouped_xyz=False, normalize_xyz=False, uniform_sample=False,
@@ -186,13 +215,15 @@ class QueryAndGroup(nn.Module):
             assert self.uniform_sample, \
                 'uniform_sample should be True when returning the count of unique samples'
         if self.max_radius is None:
-            raise NotImplementedError(
-                'kNN grouping (max_radius=None) is outside the VoteNet/Nesie hot path '
-                '(SURVEY.md 2a #30): every shipped config gives a radius')
-        if self.uniform_sample:
-            raise NotImplementedError('uniform_sample is not used by any shipped config')
+            assert not self.normalize_xyz, \
+                'can not normalize grouped xyz when max_radius is None'
+        self.generator = None   # torch.Generator of the uniform_sample draws (None: the default one)
 
     def ball_indices(self, points_xyz, center_xyz):
+        """The neighbourhood indices (B, npoint, sample_num) of this grouper: the ball query, or
+        with ``max_radius=None`` the kNN indices (the name is the pipelined callers')."""
+        if self.max_radius is None:
+            return knn(self.sample_num, points_xyz, center_xyz, False).transpose(1, 2).contiguous()
         return ball_query(self.min_radius, self.max_radius, self.sample_num, points_xyz,
                           center_xyz)
 
@@ -201,9 +232,11 @@ class QueryAndGroup(nn.Module):
         for exactly these points/centres (they depend on coordinates only, never on weights);
         ``csr`` (optional) = ``inverted_index(idx, N)`` for the backward gather-sum."""
         if idx is None:
-            idx = ball_query(self.min_radius, self.max_radius, self.sample_num, points_xyz,
-                             center_xyz)
+            idx = self.ball_indices(points_xyz, center_xyz)
+        if self.uniform_sample:     # always the literal grouping below
+            idx, unique_cnt = uniform_resample(idx, self.generator)
         if (features is not None and self.use_xyz and not self.return_grouped_xyz
+                and not self.uniform_sample
                 and not self.return_grouped_idx and not points_xyz.requires_grad
                 and not center_xyz.requires_grad):
             return QueryGroupCat.apply(points_xyz, center_xyz, features, idx,
@@ -228,6 +261,8 @@ class QueryAndGroup(nn.Module):
         ret = [new_features]
         if self.return_grouped_xyz:
             ret.append(grouped_xyz)
+        if self.return_unique_cnt:
+            ret.append(unique_cnt)
         if self.return_grouped_idx:
             ret.append(idx)
         return ret[0] if len(ret) == 1 else tuple(ret)

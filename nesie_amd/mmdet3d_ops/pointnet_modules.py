@@ -238,6 +238,9 @@ class BasePointSAModule(nn.Module):
         self.pool_mod = pool_mod
         self.fps_mod_list, self.fps_sample_range_list = fps_mod, fps_sample_range_list
         self.points_sampler = Points_Sampler(self.num_point, fps_mod, fps_sample_range_list)
+        if dilated_group and any(r is None for r in radii):
+            raise AssertionError('dilated_group needs a radius per scale: a None radius groups '
+                                 'the nearest neighbours, which have no inner radius')
         # dilated grouping: scale i only takes neighbours beyond the previous scale's radius
         inner = [0] + list(radii[:-1]) if dilated_group else [0] * scales
         self.groupers = nn.ModuleList(
