@@ -366,6 +366,22 @@ int nesie_lhs_nms_samecls(int b, int k, const float *boxes, float thr, uint8_t *
 int nesie_iou3d_forward(int n, const float *box1, const float *box2, float *iou, float *jac,
                         void *stream);
 
+/* oriented_iou_loss.py:112-152  cal_giou_3d / cal_diou_3d, one launch.
+ * kind 0: GIoU loss = 1 - iou3d + (v_c - u3d) / v_c,            v_c = z_range * w * h
+ * kind 1: DIoU loss = 1 - iou3d + d2 / c2,  c2 = w*w + h*h + z_range*z_range, d2 = |centre1 - centre2|^2
+ * enclosing 0: "smallest" (min_enclosing_box.py:142-172), 1: "aligned" (oriented_iou_loss.py:166-194)
+ * loss[n], iou[n] (may be NULL), jac[n,7] = d loss / d box1 (may be NULL: values only); box2 constant.
+ * iou3d, u3d and z_range = max(zmax) - min(zmin), clamped at 0, are those of cal_iou_3d(verbose=True):
+ * the same per-pair chain as nesie_iou3d_forward, and iou[] holds its bits.  (w, h) of "smallest" is
+ * the reference's brute force over its 24 candidate hull edges in fp32 and in its order of
+ * operations (slope (y2-y1)/(x2-x1+1e-8), projection range over all 8 corners, distance range over
+ * the other 6 with sqrt(dy^2+dx^2+1e-14), area + 1e8 where it is exactly 0, first minimum); max,
+ * min and arg-min are piecewise constant in the Jacobian, as autograd treats them.
+ * A negative n, an unknown kind or enclosing, or a null box1 / box2 / loss with n > 0 is
+ * NESIE_ERR_INVALID_ARG; n == 0 succeeds without a launch. */
+int nesie_giou3d_forward(int n, const float *box1, const float *box2, int kind, int enclosing,
+                         float *loss, float *iou, float *jac, void *stream);
+
 /* Training-mode BatchNorm with an optional fused ReLU over x[B, C, P] (statistics per
  * channel over B*P; biased variance for normalisation, unbiased for running_var, as
  * torch.nn.BatchNorm{1,2}d).  No extension entry in the reference: it builds

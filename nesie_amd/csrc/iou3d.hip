@@ -102,22 +102,23 @@ __device__ __forceinline__ void corners_of(const Dual<ND> &x, const Dual<ND> &y,
   }
 }
 
-// SPLIT (with ND = 1): eight threads per pair, thread `comp` carries the derivative with respect
-// to parameter `comp` only (the components of a dual number never mix, so every derivative is
-// the same chain of operations as in the 7-wide form: identical bits) -- a quarter of the serial
-// work per thread and eight times the threads for a kernel that is pure latency at 2 048 pairs.
+// What one (prediction, target) pair yields: the IoU chain of cal_iou_3d(verbose=True) up to the
+// 3-D IoU, with the pieces the enclosing-box losses read on top of it.
+template <int ND>
+struct PairGeom {
+  Dual<ND> b1[7], b2[7];
+  Dual<ND> c1x[4], c1y[4], c2x[4], c2y[4];   // BEV corners, box2corners_th order
+  Dual<ND> zmax1, zmin1, zmax2, zmin2;
+  Dual<ND> u3d, iou3d;
+};
+
+// The per-pair body shared by iou3d_kernel and giou3d_kernel.  SPLIT (with ND = 1): the thread
+// carries the derivative with respect to parameter `comp` only.
 template <int ND, bool SPLIT>
-__global__ __launch_bounds__(64) void iou3d_kernel(int n, const float *__restrict__ box1,
-                                                   const float *__restrict__ box2,
-                                                   float *__restrict__ iou,
-                                                   float *__restrict__ jac) {
+__device__ __forceinline__ void pair_body(const float *__restrict__ p, const float *__restrict__ q,
+                                          int comp, PairGeom<ND> &g) {
   typedef Dual<ND> D;
-  const int gid = blockIdx.x * 64 + threadIdx.x;
-  const int i = SPLIT ? gid >> 3 : gid;
-  const int comp = gid & 7;
-  if (i >= n || (SPLIT && comp == 7)) return;
-  const float *p = box1 + (size_t)i * 7, *q = box2 + (size_t)i * 7;
-  D b1[7], b2[7];
+  D (&b1)[7] = g.b1, (&b2)[7] = g.b2;
 #pragma unroll
   for (int k = 0; k < 7; ++k) {
     if (SPLIT) { b1[k] = D(p[k]); if (k == comp) b1[k].d[0] = 1.f; }
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(64) void iou3d_kernel(int n, const float *__restric
   }
 
   // ---- BEV corners -----------------------------------------------------------------
-  D c1x[4], c1y[4], c2x[4], c2y[4];
+  D (&c1x)[4] = g.c1x, (&c1y)[4] = g.c1y, (&c2x)[4] = g.c2x, (&c2y)[4] = g.c2y;
   corners_of(b1[0], b1[1], b1[3], b1[4], b1[6], c1x, c1y);
   corners_of(b2[0], b2[1], b2[3], b2[4], b2[6], c2x, c2y);
 
@@ -209,19 +210,226 @@ __global__ __launch_bounds__(64) void iou3d_kernel(int n, const float *__restric
   const D area1 = b1[3] * b1[4], area2 = b2[3] * b2[4];
   const D uni = area1 + area2 - inter;
   const D iou2d = inter / uni;
-  const D zmax1 = b1[2] + b1[5] * 0.5f, zmin1 = b1[2] - b1[5] * 0.5f;
-  const D zmax2 = b2[2] + b2[5] * 0.5f, zmin2 = b2[2] - b2[5] * 0.5f;
-  D zov = dmin(zmax1, zmax2) - dmax(zmin1, zmin2);
+  g.zmax1 = b1[2] + b1[5] * 0.5f; g.zmin1 = b1[2] - b1[5] * 0.5f;
+  g.zmax2 = b2[2] + b2[5] * 0.5f; g.zmin2 = b2[2] - b2[5] * 0.5f;
+  D zov = dmin(g.zmax1, g.zmax2) - dmax(g.zmin1, g.zmin2);
   if (zov.v < 0.f) zov = D(0.f);  // clamp_min(0)
   const D inter3 = iou2d * uni * zov;
   const D v1 = b1[3] * b1[4] * b1[5], v2 = b2[3] * b2[4] * b2[5];
-  const D out = inter3 / (v1 + v2 - inter3);
+  g.u3d = v1 + v2 - inter3;
+  g.iou3d = inter3 / g.u3d;
+}
+
+// SPLIT (with ND = 1): eight threads per pair, thread `comp` carries the derivative with respect
+// to parameter `comp` only (the components of a dual number never mix, so every derivative is
+// the same chain of operations as in the 7-wide form: identical bits) -- a quarter of the serial
+// work per thread and eight times the threads for a kernel that is pure latency at 2 048 pairs.
+template <int ND, bool SPLIT>
+__global__ __launch_bounds__(64) void iou3d_kernel(int n, const float *__restrict__ box1,
+                                                   const float *__restrict__ box2,
+                                                   float *__restrict__ iou,
+                                                   float *__restrict__ jac) {
+  const int gid = blockIdx.x * 64 + threadIdx.x;
+  const int i = SPLIT ? gid >> 3 : gid;
+  const int comp = gid & 7;
+  if (i >= n || (SPLIT && comp == 7)) return;
+  PairGeom<ND> g;
+  pair_body<ND, SPLIT>(box1 + (size_t)i * 7, box2 + (size_t)i * 7, comp, g);
+  const Dual<ND> &out = g.iou3d;
   if (SPLIT) {
     if (comp == 0) iou[i] = out.v;
     jac[(size_t)i * 7 + comp] = out.d[0];
     return;
   }
   iou[i] = out.v;
+  if (ND > 0) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) jac[(size_t)i * 7 + k] = out.d[k];
+  }
+}
+
+// ---- enclosing boxes of the 8 BEV corners (cal_giou_3d / cal_diou_3d) ---------------------------
+template <int ND>
+__device__ __forceinline__ Dual<ND> dsqrt(const Dual<ND> &a) {
+  Dual<ND> r;
+  r.v = sqrtf(a.v);
+  const float c = 0.5f / r.v;
+#pragma unroll
+  for (int i = 0; i < ND; ++i) r.d[i] = c * a.d[i];
+  return r;
+}
+template <int ND>
+__device__ __forceinline__ Dual<ND> dabs(const Dual<ND> &a) {   // sign(0) = 0, as torch.abs
+  Dual<ND> r;
+  r.v = fabsf(a.v);
+  const float s = a.v > 0.f ? 1.f : (a.v < 0.f ? -1.f : 0.f);
+#pragma unroll
+  for (int i = 0; i < ND; ++i) r.d[i] = s * a.d[i];
+  return r;
+}
+// torch.max / torch.min of two tensors: on a tie each side gets half the gradient
+template <int ND>
+__device__ __forceinline__ Dual<ND> dhalf_tie(const Dual<ND> &a, const Dual<ND> &b) {
+  Dual<ND> r;
+  r.v = a.v;
+#pragma unroll
+  for (int i = 0; i < ND; ++i) r.d[i] = 0.5f * a.d[i] + 0.5f * b.d[i];
+  return r;
+}
+template <int ND>
+__device__ __forceinline__ Dual<ND> dmax_tie(const Dual<ND> &a, const Dual<ND> &b) {
+  return a.v > b.v ? a : (b.v > a.v ? b : dhalf_tie(a, b));
+}
+template <int ND>
+__device__ __forceinline__ Dual<ND> dmin_tie(const Dual<ND> &a, const Dual<ND> &b) {
+  return a.v < b.v ? a : (b.v < a.v ? b : dhalf_tie(a, b));
+}
+
+// One candidate of min_enclosing_box.py: the box with a side along the line through corners i < j.
+// w = the range of the projections of all 8 corners onto the line (:116-139), h = the range of the
+// distances of the other 6 from it (:87-113); every expression in the reference's order.  A max or
+// min over a dimension takes the first of equal entries in the reference's order of the points
+// (the line's two, then the others ascending), which decides whose derivative an exact tie gets.
+template <int ND>
+__device__ __forceinline__ void enclosing_candidate(const Dual<ND> (&px)[8], const Dual<ND> (&py)[8],
+                                                    int i, int j, Dual<ND> &w, Dual<ND> &h) {
+  typedef Dual<ND> D;
+  D x1 = px[0], y1 = py[0], x2 = px[1], y2 = py[1];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    if (k == i) { x1 = px[k]; y1 = py[k]; }
+    if (k == j) { x2 = px[k]; y2 = py[k]; }
+  }
+  const D dx = x2 - x1, dy = y2 - y1;
+  const D slope = dy / (dx + 1e-8f);
+  D nrm;   // |(1, slope)|: only its value is read
+  nrm.v = sqrtf(slope.v * slope.v + 1.f);
+  const D num = dsqrt(dy * dy + dx * dx + 1e-14f);
+  const float inf = __builtin_inff();
+  // projections on values; the two corners that give the range keep their derivatives
+  float pmax = (x1.v + y1.v * slope.v) / nrm.v, pmin = pmax;
+  D xa = x1, ya = y1, xb = x1, yb = y1;
+  {
+    const float pr = (x2.v + y2.v * slope.v) / nrm.v;
+    if (pr > pmax) { pmax = pr; xa = x2; ya = y2; }
+    if (pr < pmin) { pmin = pr; xb = x2; yb = y2; }
+  }
+  D dmx(-inf), dmn(inf), amx(-1.f);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    if (k == i || k == j) continue;
+    const float pr = (px[k].v + py[k].v * slope.v) / nrm.v;
+    if (pr > pmax) { pmax = pr; xa = px[k]; ya = py[k]; }
+    if (pr < pmin) { pmin = pr; xb = px[k]; yb = py[k]; }
+    const D d = (dy * px[k] - dx * py[k] + x2 * y1 - y2 * x1) / num;
+    const D a = dabs(d);
+    if (d.v > dmx.v) dmx = d;
+    if (d.v < dmn.v) dmn = d;
+    if (a.v > amx.v) amx = a;
+  }
+  // w = proj(a) - proj(b) = (ex + slope * ey) / nrm with e = a - b.  Its derivative is taken of
+  // that one quotient with the slope terms collected, (ex' + slope ey') / nrm + slope' (ey - slope
+  // ex) / nrm^3: the same derivative as of the two projections one by one, without the
+  // cancellation between slope' ey / nrm and w nrm' / nrm, each ~1e8 x the result on an edge
+  // that is vertical (slope = dy / 1e-8).
+  w.v = pmax - pmin;
+  {
+    const D ex = xa - xb, ey = ya - yb;
+    const float t = (ey.v - slope.v * ex.v) / (nrm.v * nrm.v);
+#pragma unroll
+    for (int c = 0; c < ND; ++c) w.d[c] = ((ex.d[c] + slope.v * ey.d[c]) + slope.d[c] * t) / nrm.v;
+  }
+  h = dmax_tie(dmx - dmn, amx);
+}
+
+// ENCLOSING 0 "smallest": the 24 candidate areas on values only, the first minimum wins (area
+// + 1e8 where it is exactly 0), then the winner's (w, h) again with derivatives.  1 "aligned":
+// the x and y ranges of the corners, per box first and then across (oriented_iou_loss.py:166-194).
+template <int ND, int ENCLOSING>
+__device__ __forceinline__ void enclosing_box(const PairGeom<ND> &g, Dual<ND> &w, Dual<ND> &h) {
+  typedef Dual<ND> D;
+  if (ENCLOSING == 1) {
+    D x1mx = g.c1x[0], x1mn = g.c1x[0], y1mx = g.c1y[0], y1mn = g.c1y[0];
+    D x2mx = g.c2x[0], x2mn = g.c2x[0], y2mx = g.c2y[0], y2mn = g.c2y[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      if (g.c1x[k].v > x1mx.v) x1mx = g.c1x[k];
+      if (g.c1x[k].v < x1mn.v) x1mn = g.c1x[k];
+      if (g.c1y[k].v > y1mx.v) y1mx = g.c1y[k];
+      if (g.c1y[k].v < y1mn.v) y1mn = g.c1y[k];
+      if (g.c2x[k].v > x2mx.v) x2mx = g.c2x[k];
+      if (g.c2x[k].v < x2mn.v) x2mn = g.c2x[k];
+      if (g.c2y[k].v > y2mx.v) y2mx = g.c2y[k];
+      if (g.c2y[k].v < y2mn.v) y2mn = g.c2y[k];
+    }
+    w = dmax_tie(x1mx, x2mx) - dmin_tie(x1mn, x2mn);
+    h = dmax_tie(y1mx, y2mx) - dmin_tie(y1mn, y2mn);
+    return;
+  }
+  D px[8], py[8];
+  Dual<0> vx[8], vy[8];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    px[k] = g.c1x[k]; py[k] = g.c1y[k]; px[4 + k] = g.c2x[k]; py[4 + k] = g.c2y[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { vx[k].v = px[k].v; vy[k].v = py[k].v; }
+  float best = __builtin_inff();
+  int bi = 0, bj = 1;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+#pragma unroll
+    for (int j = i + 1; j < 8; ++j) {
+      if ((i == 0 && j == 2) || (i == 1 && j == 3) || (i == 5 && j == 7) || (i == 4 && j == 6))
+        continue;   // a diagonal of one box is never a hull edge
+      Dual<0> cw, ch;
+      enclosing_candidate(vx, vy, i, j, cw, ch);
+      float area = cw.v * ch.v;
+      if (area == 0.f) area += 1e8f;
+      if (area < best) { best = area; bi = i; bj = j; }
+    }
+  }
+  enclosing_candidate(px, py, bi, bj, w, h);
+}
+
+template <int ND, bool SPLIT, int ENCLOSING>
+__global__ __launch_bounds__(64) void giou3d_kernel(int n, const float *__restrict__ box1,
+                                                    const float *__restrict__ box2, int kind,
+                                                    float *__restrict__ loss,
+                                                    float *__restrict__ iou,
+                                                    float *__restrict__ jac) {
+  typedef Dual<ND> D;
+  const int gid = blockIdx.x * 64 + threadIdx.x;
+  const int i = SPLIT ? gid >> 3 : gid;
+  const int comp = gid & 7;
+  if (i >= n || (SPLIT && comp == 7)) return;
+  PairGeom<ND> g;
+  pair_body<ND, SPLIT>(box1 + (size_t)i * 7, box2 + (size_t)i * 7, comp, g);
+  D w, h;
+  enclosing_box<ND, ENCLOSING>(g, w, h);
+  D zr = dmax_tie(g.zmax1, g.zmax2) - dmin_tie(g.zmin1, g.zmin2);
+  if (zr.v < 0.f) zr = D(0.f);  // clamp_min(0)
+  D extra;
+  if (kind == 0) {
+    const D vc = zr * w * h;
+    extra = (vc - g.u3d) / vc;
+  } else {
+    const D xo = g.b1[0] - g.b2[0], yo = g.b1[1] - g.b2[1], zo = g.b1[2] - g.b2[2];
+    const D d2 = xo * xo + yo * yo + zo * zo;
+    const D c2 = w * w + h * h + zr * zr;
+    extra = d2 / c2;
+  }
+  const D out = -g.iou3d + 1.f + extra;   // 1. - iou3d + extra
+  if (SPLIT) {
+    if (comp == 0) {
+      loss[i] = out.v;
+      if (iou) iou[i] = g.iou3d.v;
+    }
+    jac[(size_t)i * 7 + comp] = out.d[0];
+    return;
+  }
+  loss[i] = out.v;
+  if (iou) iou[i] = g.iou3d.v;
   if (ND > 0) {
 #pragma unroll
     for (int k = 0; k < ND; ++k) jac[(size_t)i * 7 + k] = out.d[k];
@@ -244,5 +452,28 @@ extern "C" int nesie_iou3d_forward(int n, const float *box1, const float *box2, 
   else
     hipLaunchKernelGGL((iou3d_kernel<0, false>), dim3(cdiv(n, 64)), dim3(64), 0,
                        (hipStream_t)stream, n, box1, box2, iou, jac);
+  return check_launch(W);
+}
+
+template <int ENCLOSING>
+static void launch_giou3d(int n, const float *box1, const float *box2, int kind, float *loss,
+                          float *iou, float *jac, hipStream_t stream) {
+  if (jac)
+    hipLaunchKernelGGL((giou3d_kernel<1, true, ENCLOSING>), dim3(cdiv((long long)n * 8, 64)),
+                       dim3(64), 0, stream, n, box1, box2, kind, loss, iou, jac);
+  else
+    hipLaunchKernelGGL((giou3d_kernel<0, false, ENCLOSING>), dim3(cdiv(n, 64)), dim3(64), 0,
+                       stream, n, box1, box2, kind, loss, iou, jac);
+}
+
+extern "C" int nesie_giou3d_forward(int n, const float *box1, const float *box2, int kind,
+                                    int enclosing, float *loss, float *iou, float *jac,
+                                    void *stream) {
+  const char *W = "giou3d_forward";
+  NESIE_REQUIRE(n >= 0 && (kind == 0 || kind == 1) && (enclosing == 0 || enclosing == 1), W);
+  if (n == 0) return NESIE_OK;
+  NESIE_REQUIRE(box1 && box2 && loss, W);
+  if (enclosing == 0) launch_giou3d<0>(n, box1, box2, kind, loss, iou, jac, (hipStream_t)stream);
+  else launch_giou3d<1>(n, box1, box2, kind, loss, iou, jac, (hipStream_t)stream);
   return check_launch(W);
 }

@@ -658,6 +658,21 @@ class HipKernels:
             assert jac.numel() == n * 7
         _launch("nesie_iou3d_forward", box1, n, box1, box2, iou, jac)
 
+    def giou3d_forward(self, box1, box2, kind, enclosing, loss, iou, jac):
+        """box1, box2 (n,7); kind 0 GIoU / 1 DIoU; enclosing 0 smallest / 1 aligned; loss (n,);
+        iou (n,) or None; jac (n,7) = d loss / d box1, or None (nesie_giou3d_forward)."""
+        _check(box1, box2, loss); _f32(box1, box2, loss)
+        n = loss.numel()
+        assert box1.numel() == n * 7 and box2.numel() == n * 7
+        if iou is not None:
+            _check(iou); _f32(iou)
+            assert iou.numel() == n
+        if jac is not None:
+            _check(jac); _f32(jac)
+            assert jac.numel() == n * 7
+        _launch("nesie_giou3d_forward", box1, n, box1, box2, int(kind), int(enclosing), loss, iou,
+                jac)
+
     def conv_wgrad(self, dy, x, dw, x_coef=None, x_relu=False, bn_z=None, bnb=None):
         """dw (cout, cin) = sum_b dy[b] (cout, P) @ act(x[b]) (cin, P)^T on the matrix cores;
         dy and x may be batch-strided views (each dy[b], x[b] contiguous).  bn_z / bnb: dy is the

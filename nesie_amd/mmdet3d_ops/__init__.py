@@ -16,7 +16,7 @@ from .pointnet_modules import (ConvModule, PointFPModule, PointSAModule, PointSA
 from .knn import knn
 from .iou3d import batched_nms_bev, boxes_iou_bev, boxes_overlap_bev, nms_gpu, nms_normal_gpu
 from .roiaware_pool3d import points_in_boxes_batch, points_in_boxes_count
-from .rotated_iou import cal_iou_3d, sort_v
+from .rotated_iou import cal_giou_3d, cal_iou_3d, sort_v
 
 _HOT = [
     'ball_query', 'furthest_point_sample', 'furthest_point_sample_with_dist',
@@ -24,7 +24,7 @@ _HOT = [
     'GroupAll', 'QueryAndGroup', 'PointSAModule', 'PointSAModuleMSG', 'PointFPModule',
     'points_in_boxes_batch', 'Points_Sampler', 'build_sa_module', 'cal_iou_3d', 'sort_v',
     'ConvModule', 'boxes_overlap_bev', 'points_in_boxes_count',
-    'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu', 'knn',
+    'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu', 'knn', 'cal_giou_3d',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
@@ -34,7 +34,6 @@ _OUT_OF_SCOPE = [
     'RoIAwarePool3d', 'points_in_boxes_gpu', 'points_in_boxes_cpu',
     'make_sparse_convmodule', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
     'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule', 'PAConvCUDASAModuleMSG',
-    'cal_giou_3d',
 ]
 __all__ = _HOT + _OUT_OF_SCOPE
 

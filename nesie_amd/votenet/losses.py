@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..mmdet3d_ops.rotated_iou import cal_iou_3d
+from ..mmdet3d_ops.rotated_iou import cal_diou_3d, cal_giou_3d, cal_iou_3d
 
 
 # ---- mmdet loss plumbing (appendix C) ------------------------------------------
@@ -213,6 +213,43 @@ class IoU3DLoss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
+# ---- GIoU3D / DIoU3D (iou3d_loss.py:16-18, 38-68, 78-81) ---------------------------
+class _EnclosingIoU3DLoss(nn.Module):
+    """IoU3DMixin around an enclosing-box loss.  Deliberately not an ``IoU3DLoss``: the fused
+    head-loss kernel computes plain IoU and must keep refusing a head with one of these."""
+
+    loss_function = None
+
+    def __init__(self, reduction='mean', loss_weight=1.0, enclosing_type='smallest'):
+        super().__init__()
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.enclosing_type = enclosing_type
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None,
+                **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        if weight is not None and weight.dim() > 1:
+            weight = weight.mean(-1)
+        # the reference's `[0][0]`: the loss of (loss, iou), then the batch axis added here
+        loss = type(self).loss_function(pred[None, ...], target[None, ...],
+                                        self.enclosing_type)[0][0]  # (N,)
+        if weight is not None:
+            # as IoU3DLoss: zeros where no weight is positive, without the host sync of :53-54
+            loss = torch.where(weight > 0, loss, torch.zeros_like(loss))
+        return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+class GIoU3DLoss(_EnclosingIoU3DLoss):
+    loss_function = staticmethod(cal_giou_3d)
+
+
+class DIoU3DLoss(_EnclosingIoU3DLoss):
+    """The reference has ``cal_diou_3d`` but no loss class; the name follows its pattern."""
+    loss_function = staticmethod(cal_diou_3d)
+
+
 # ---- quality focal loss (gfocal_loss.py:9-51, 80-139) ---------------------------
 def quality_focal_loss(pred, target, beta=2.0, use_sigmoid=True):
     label, score = target
@@ -252,7 +289,8 @@ class GeneralQualityFocalLoss(nn.Module):
 
 
 _LOSSES = dict(ChamferDistance=ChamferDistance, CrossEntropyLoss=CrossEntropyLoss,
-               IoU3DLoss=IoU3DLoss, GeneralQualityFocalLoss=GeneralQualityFocalLoss,
+               IoU3DLoss=IoU3DLoss, GIoU3DLoss=GIoU3DLoss, DIoU3DLoss=DIoU3DLoss,
+               GeneralQualityFocalLoss=GeneralQualityFocalLoss,
                SurfaceLoss=SurfaceLoss, SidePredLoss=SidePredLoss, MSELoss=MSELoss,
                L1Loss=L1Loss, SmoothL1Loss=SmoothL1Loss)
 
