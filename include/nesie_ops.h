@@ -644,6 +644,36 @@ int nesie_pool_tail_wgrad(int nb, int k, int c, long long p, int ns, const float
                           const float *ab, const float *w, float *part_m, float *part_s,
                           float *part_w, double *ms, float *dw, void *stream);
 
+/* A convolution (k -> c = 128, bias-free) that is max-pooled DIRECTLY over groups of ns positions (the
+ * MiniPointNet's conv4 + max, side_pooling_module.py:343-370; autograd's max_pool2d / conv2d backward
+ * in the reference): the gradient of its output is one non-zero per channel and group, and its
+ * backward runs from the ENTRIES instead of the dense (nb, c, p) tensor.
+ * nesie_pool_tail_pack: ent [nb][m][c][2] = (grad_pooled masked by pooled > 0 -- pooled NULL: no mask
+ *   --, arg-max position as int bits); grad_pooled / pooled / argmax (nb, c, m); c % 32 == 0.
+ * nesie_pw_dgrad_bn_reduce_sparse: nesie_pw_dgrad_bn_reduce with x given as ent (c = 128, ns in
+ *   {16, 32, 64}, p % 64 == 0): the same launch parameters, y and bn_part bit for bit the dense
+ *   launch's; nslots = nesie_pw_stat_slots(nb, ng, 128, cout, p).
+ * nesie_pw_wgrad_sparse / _deferred: nesie_pw_wgrad / nesie_pw_wgrad_deferred (below) with dy given as ent
+ *   (co = 128, ci = 256, ns in {16, 64}; x_coef required, act = relu): a sparse product on the vector
+ *   ALUs, one pass over x, that walks the dense launch's tiles and leaves the dense launch's partials --
+ *   dw is bit for bit what nesie_pw_wgrad computes from the expanded tensor; same workspace size
+ *   (nesie_pw_wgrad_workspace_bytes), same reduction, same rules for a deferred one. */
+int nesie_pool_tail_pack(int nb, int c, int m, const float *grad_pooled, const float *pooled,
+                         const uint8_t *argmax, float *ent, void *stream);
+int nesie_pw_dgrad_bn_reduce_sparse(int nb, int ng, int c, int cout, long long p, int ns,
+                                    const float *ent, const float *w, long long w_gstride,
+                                    int w_rstride, int w_cstride, float *y, long long y_bstride,
+                                    const float *bn_z, long long bnz_bstride, const float *bn_coef,
+                                    float *bn_part, void *stream);
+int nesie_pw_wgrad_sparse_supported(int co, int ci, long long p, int ns);
+int nesie_pw_wgrad_sparse(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
+                          const float *x, long long x_bstride, const float *x_coef, float *dw,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int nesie_pw_wgrad_sparse_deferred(int nb, int ng, int co, int ci, long long p, int ns,
+                                   const float *ent, const float *x, long long x_bstride,
+                                   const float *x_coef, float *dw, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 /* Weight gradient of the same layers: dw[g][co][ci] = sum over the batches n of group g (n % ng
  * == g) and all positions of dy[n][co][pos] * act(x[n][ci][pos]), act as in
  * nesie_pw_layer_forward (x_coef [ng*ci][4], NULL = identity): the Conv2d weight gradient that

@@ -74,7 +74,8 @@ __global__ __launch_bounds__(1024) void pt_reduce_kernel(int nb, int c_all, int 
   }
 }
 
-// ent[n][group][c] = (g masked by the ReLU, position of the arg-max inside the group)
+// ent[n][group][c] = (g masked by the ReLU, position of the arg-max inside the group);
+// pooled == NULL: no mask (a convolution that is pooled directly, without norm and ReLU)
 __global__ __launch_bounds__(256) void pt_pack_kernel(int c_all, int m, const float *__restrict__ g,
                                                       const float *__restrict__ pooled,
                                                       const uint8_t *__restrict__ arg,
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256) void pt_pack_kernel(int c_all, int m, const fl
     const int j = m0 + tx;
     if (j < m) {
       const size_t o = ((size_t)n * c_all + c0 + r) * m + j;
-      tile[r][tx] = make_float2(pooled[o] > 0.f ? g[o] : 0.f, __int_as_float((int)arg[o]));
+      tile[r][tx] = make_float2(!pooled || pooled[o] > 0.f ? g[o] : 0.f, __int_as_float((int)arg[o]));
     }
   }
   __syncthreads();
@@ -353,6 +354,18 @@ static int pt_gram_groups(int nb, long long p) {
 }  // namespace nesie
 
 using namespace nesie;
+
+// The entries alone: ent[n][m][c] = (grad_pooled masked by pooled > 0 -- pooled == NULL: unmasked --,
+// arg-max position inside the group), the layout PW_SPARSE128 and the sparse weight gradient read
+extern "C" int nesie_pool_tail_pack(int nb, int c, int m, const float *grad_pooled, const float *pooled,
+                                    const uint8_t *argmax, float *ent, void *stream) {
+  const char *W = "pool_tail_pack";
+  NESIE_REQUIRE(nb >= 1 && nb <= 65535 && c >= 32 && c % 32 == 0 && c / 32 <= 65535 && m >= 1, W);
+  NESIE_REQUIRE(grad_pooled && argmax && ent && ((uintptr_t)ent & 7) == 0, W);
+  hipLaunchKernelGGL(pt_pack_kernel, dim3(cdiv(m, 32), c / 32, nb), dim3(256), 0, (hipStream_t)stream, c, m,
+                     grad_pooled, pooled, argmax, (float2 *)ent);
+  return check_launch(W);
+}
 
 extern "C" int nesie_pool_tail_supported(int k, int c, long long p, int ns) {
   PtGeom g;

@@ -18,6 +18,8 @@ PW_GEOM_DECL(9, 1, 8, 1, 1)    // K <= 144
 PW_GEOM_DECL(8, 2, 8, 1, 1)    // K <= 256
 PW_GEOM_DECL(9, 2, 8, 1, 1)    // K <= 288
 PW_GEOM_DECL(8, 4, 8, 1, 1)    // K <= 512
+// K = 128 with every operand row built from a max-pool's entries (pwconv_g10.hip)
+int pw_launch_sparse_8_1_8_1_1(const PwFwd &a, int grid, size_t lds, hipStream_t s);
 
 // Chan merge of the per-wave partials -> (scale, bias, mean, invstd) + running statistics.
 // One 64-thread block per channel (channel index runs over ng * cout: stacked layers).
@@ -201,10 +203,10 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
                            uint8_t *arg_max_out, uint8_t *arg_min_out, const float *bn_z,
                            long long bnz_bstride, const float *bn_coef, float *bn_part,
                            void *stream, const float *k4_w = nullptr, int k4_in = 0,
-                           float *k4_gpart = nullptr) {
+                           float *k4_gpart = nullptr, const float *sp_ent = nullptr, int sp_ns = 0) {
   NESIE_REQUIRE(nb >= 0 && ng >= 1 && k >= 1 && cout >= 1 && p >= 0, W);
   if (nb == 0 || p == 0) return NESIE_OK;
-  NESIE_REQUIRE(nb % ng == 0 && x && w, W);
+  NESIE_REQUIRE(nb % ng == 0 && (x || sp_ent) && w, W);
   PwGeom g;
   if (!pw_geometry(k, cout, &g) || p % g.pt != 0 || (long long)(k > cout ? k : cout) * p >= (1ll << 30)) {
     set_error("%s: %d -> %d over %lld positions is outside the built tiles", W, k, cout, p);
@@ -241,7 +243,13 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
     epi |= PW_POOL | (pool_min ? PW_POOLMIN : 0);
     pg = pool_group;
   }
+  if (sp_ent) {     // every operand row is built from the entries (PW_SPARSE128 with SPC == K): no x
+    NESIE_REQUIRE(k == 128 && cout % 128 == 0 && epi == (PW_STORE | PW_BNRED) && ((uintptr_t)sp_ent & 7) == 0, W);
+    NESIE_REQUIRE((sp_ns == 16 || sp_ns == 32 || sp_ns == 64) && p % 64 == 0, W);
+  }
   PwFwd a;
+  a.sp_ent = (const float2 *)sp_ent; a.sp_ns_shift = sp_ent ? __builtin_ctz((unsigned)sp_ns) : 0;
+  a.sp_groups = sp_ent ? (int)(p / sp_ns) : 0;
   a.x = x; a.x_bs = x_bstride; a.p = p; a.nb = nb; a.k = k;
   a.w = w; a.w_gs = w_gstride; a.w_rs = w_rstride; a.w_cs = w_cstride; a.ng = ng; a.cout = cout;
   a.in_coef = in_coef; a.in_lo = in_relu ? 0.f : -__builtin_inff();
@@ -274,8 +282,12 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
 #ifdef PW_DEV
   G(8, 2, 8, 1, 1); G(8, 1, 8, 1, 1);
 #else
-  G(4, 1, 4, 1, 1); G(4, 1, 4, 1, 2); G(8, 1, 4, 1, 1); G(8, 1, 8, 1, 1);
-  G(9, 1, 8, 1, 1); G(8, 2, 8, 1, 1); G(9, 2, 8, 1, 1); G(8, 4, 8, 1, 1);
+  if (sp_ent) {
+    st = pw_launch_sparse_8_1_8_1_1(a, grid, lds, s);
+  } else {
+    G(4, 1, 4, 1, 1); G(4, 1, 4, 1, 2); G(8, 1, 4, 1, 1); G(8, 1, 8, 1, 1);
+    G(9, 1, 8, 1, 1); G(8, 2, 8, 1, 1); G(9, 2, 8, 1, 1); G(8, 4, 8, 1, 1);
+  }
 #endif
 #undef G
   if (st != NESIE_OK) {
@@ -316,6 +328,27 @@ extern "C" int nesie_pw_dgrad_bn_reduce(int nb, int ng, int k, int cout, long lo
   return pw_forward_impl(W, nb, ng, k, cout, p, x, x_bstride, w, w_gstride, w_rstride, w_cstride,
                          nullptr, 0, nullptr, 0, nullptr, y, y_bstride, nullptr, 0, 0, nullptr,
                          nullptr, nullptr, nullptr, bn_z, bnz_bstride, bn_coef, bn_part, stream);
+}
+
+// nesie_pw_dgrad_bn_reduce for an x that is the gradient a max over groups of ns positions hands
+// back -- one non-zero per channel and group -- given as entries ent[n][group][c] = (value,
+// position inside the group) (nesie_pool_tail_pack) instead of the dense (nb, 128, p) tensor.  The
+// launch is the dense one's in every parameter (grid, tile-to-workgroup map, reduction slots, weight
+// path, and the walk direction, which follows the size of the dense tensor that no longer exists):
+// the same operand values meet the same weights in the same order, y and bn_part are bit for bit
+// what the dense launch leaves.
+extern "C" int nesie_pw_dgrad_bn_reduce_sparse(int nb, int ng, int c, int cout, long long p, int ns,
+                                               const float *ent, const float *w, long long w_gstride,
+                                               int w_rstride, int w_cstride, float *y,
+                                               long long y_bstride, const float *bn_z,
+                                               long long bnz_bstride, const float *bn_coef,
+                                               float *bn_part, void *stream) {
+  const char *W = "pw_dgrad_bn_reduce_sparse";
+  NESIE_REQUIRE(ent && y && bn_z && bn_coef && bn_part && c == 128, W);
+  return pw_forward_impl(W, nb, ng, c, cout, p, nullptr, 0, w, w_gstride, w_rstride, w_cstride,
+                         nullptr, 0, nullptr, 0, nullptr, y, y_bstride, nullptr, 0, 0, nullptr,
+                         nullptr, nullptr, nullptr, bn_z, bnz_bstride, bn_coef, bn_part, stream,
+                         nullptr, 0, nullptr, ent, ns);
 }
 
 // SA1's second layer over the REBUILT output of its first: the operand rows are relu(bn(W0 . X4)),

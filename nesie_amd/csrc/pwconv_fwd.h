@@ -133,7 +133,9 @@ enum : int {
   // The first SPC = 128 / 256 operand rows are not loaded but BUILT: row c holds one value per group
   // of ns positions, sp_ent[n][group][c] = (value, position inside the group), zero elsewhere -- the
   // gradient a max-pool hands back (input gradient of a pooled tail, pool_tail.hip).  The loaded
-  // operand (x, in_coef) supplies rows SPC .. K - 1; K = KH * KT exactly.
+  // operand (x, in_coef) supplies rows SPC .. K - 1; K = KH * KT exactly.  SPC == K: every staging
+  // slot is a built row and nothing is loaded from x or in_coef (the input gradient of a convolution
+  // that is pooled directly, nesie_pw_dgrad_bn_reduce_sparse).
   PW_SPARSE128 = 256,
   PW_SPARSE256 = 512,
   // A 64-row tensor that is the raw output of a 4 -> 64 convolution, Z0 = W0 . X4 (SA1's first
@@ -218,7 +220,7 @@ void pw_fwd_kernel(const PwFwd a) {
   constexpr int CROWS = WR * RW * 16;                    // output rows per workgroup
   constexpr int SPC = (EPI & PW_SPARSE128) ? 128 : (EPI & PW_SPARSE256) ? 256 : 0;   // built operand rows
   constexpr bool K4Z = (EPI & PW_K4Z) != 0;
-  static_assert(SPC % ROWSTEP == 0 && (SPC == 0 || (NCH == NX * NT && SPC < KH * KT)), "sparse rows");
+  static_assert(SPC % ROWSTEP == 0 && (SPC == 0 || (NCH == NX * NT && SPC <= KH * KT)), "sparse rows");
   static_assert(NT % CPR == 0 && (PG == 16 || PG == 32), "tile");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   STAMP_WG(0)
@@ -948,10 +950,10 @@ static int pw_launch_epi(const PwFwd &a, int epi, int pg, int grid, size_t lds, 
 #undef GO1
 }
 
-// the one prologue / epilogue combination of a pooled tail's input gradient (built operand rows)
-template <int KT16, int KH, int WR, int WC, int RW, int SPBIT>
+// the one prologue / epilogue combination of an input gradient with built operand rows
+template <int KT16, int KH, int WR, int WC, int RW, int EPI>
 static int pw_launch_sparse(const PwFwd &a, int grid, size_t lds, hipStream_t s) {
-  auto kern = pw_fwd_kernel<KT16, KH, WR, WC, RW, PW_STORE | PW_BIAS | PW_AFFINE | PW_BNRED | SPBIT, 16, false>;
+  auto kern = pw_fwd_kernel<KT16, KH, WR, WC, RW, EPI, 16, false>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

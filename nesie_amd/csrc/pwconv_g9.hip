@@ -3,6 +3,6 @@
 #include "pwconv_fwd.h"
 namespace nesie {
 int pw_launch_sparse_6_2_4_1_1(const PwFwd &a, int grid, size_t lds, hipStream_t s) {
-  return pw_launch_sparse<6, 2, 4, 1, 1, PW_SPARSE128>(a, grid, lds, s);
+  return pw_launch_sparse<6, 2, 4, 1, 1, PW_STORE | PW_BIAS | PW_AFFINE | PW_BNRED | PW_SPARSE128>(a, grid, lds, s);
 }
 }  // namespace nesie

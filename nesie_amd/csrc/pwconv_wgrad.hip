@@ -341,6 +341,111 @@ __global__ __launch_bounds__(512, FDG ? 4 : 1) void pw_wgrad_kernel(      // (FD
       }
 }
 
+// The weight gradient of a layer whose dY is the gradient a max over groups of ns positions hands back --
+// ONE non-zero per (channel, group), given as entries ent[n][group][c] = (value, position inside the group)
+// (nesie_pool_tail_pack) -- as a sparse product on the vector ALUs, co = 128, ci = 256: no dense dY, no
+// products with zeros.  It leaves the SAME partials as pw_wgrad_kernel over the dense tensor, bit for bit:
+// there a 16x16x4 MFMA takes its four positions from one 16-position chunk, in which a channel has at most
+// one non-zero; the products with +0 leave the accumulator as it is, and the one product that remains enters
+// as a fused multiply-add.  So an element's partial is the chain fma(g, a, acc) over its workgroup's entries
+// in tile order -- reproduced here with the same tile-to-workgroup map (32-position tiles t = rank, rank +
+// nwg, ..., mirrored for big operands) and the same partial layout, plain or tiled; the reduce kernels, the
+// deferred reductions and the workspace are pw_wgrad's own.  512 threads stream act(x) tiles (256 x 32)
+// through two LDS buffers, loads two tiles ahead in registers; wave (cw, kw): channels 64 cw + lane, rows
+// 64 kw .. + 63, per entry one LDS column read (bank (4 k + position) % 64: conflict-free, equal positions
+// broadcast) and one FMA per row.
+__global__ __launch_bounds__(512) void pw_wgrad_sparse_kernel(int nb, int ng, long long p, const float *__restrict__ x,
+                                                              long long x_bs, const float *__restrict__ coef,
+                                                              const float2 *__restrict__ ent, int ns_shift,
+                                                              int groups, float *__restrict__ partial, int nwg,
+                                                              int rev, int tiled) {
+  constexpr int K = 256, CSP = 128, PT = 32, PITCH = PT + 4, CPR = PT / 4, NT = 512;
+  constexpr int NX = K * CPR / NT, ROWSTEP = NT / CPR;
+  constexpr int CW = CSP / 64, KW = 8 / CW, KPER = K / KW;
+  constexpr int TILE = K * PITCH;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cw = wave % CW, kw = wave / CW;
+  const int g = blockIdx.x % ng, rank = blockIdx.x / ng;
+  // slot i of a thread: row i ROWSTEP + tid / CPR, 16-byte column tid % CPR
+  const int srow = tid / CPR, scol = tid % CPR;
+  const unsigned goff0 = (unsigned)(((size_t)srow * p + scol * 4) * 4);
+  const unsigned gstep = (unsigned)((size_t)ROWSTEP * p * 4);
+  const unsigned lw0 = (unsigned)((srow * PITCH + scol * 4) * 4);
+  float2 *cl = (float2 *)(lds + 2 * TILE);          // (scale, bias) of the K rows
+  if (tid < K) cl[tid] = *(const float2 *)(coef + ((size_t)g * K + tid) * 4);
+  const int tpb = (int)(p / PT);
+  const int ntiles = (nb / ng) * tpb;
+  f32x4 stg[NX];
+  auto load_tile = [&](int t) {
+    t = t < ntiles ? t : ntiles - 1;
+    t = rev ? ntiles - 1 - t : t;
+    const float *xb = x + (size_t)(g + ng * (t / tpb)) * x_bs + (size_t)(t % tpb) * PT;   // uniform
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      unsigned o = goff0 + (unsigned)i * gstep;
+      asm volatile("" : "+v"(o));
+      stg[i] = load16_saddr(o, xb);
+    }
+  };
+  auto write_tile = [&](float *buf) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      f32x4 q = stg[i];
+      const float2 co = cl[i * ROWSTEP + srow];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) q[e] = fmaxf(__builtin_fmaf(q[e], co.x, co.y), 0.f);
+      *(f32x4 *)((char *)buf + lw0 + i * ROWSTEP * PITCH * 4) = q;
+    }
+  };
+  float wacc[KPER];
+#pragma unroll
+  for (int kk = 0; kk < KPER; ++kk) wacc[kk] = 0.f;
+  const int ngt = ns_shift == 4 ? 2 : 1;         // groups that meet a tile: two of 16, or half of one of 64
+  float *b0 = lds, *b1 = lds + TILE;
+  int t = rank;
+  __syncthreads();                               // cl
+  if (t < ntiles) {
+    load_tile(t);
+    write_tile(b0);
+    load_tile(t + nwg);
+  }
+  for (; t < ntiles; t += nwg) {
+    const int tt = rev ? ntiles - 1 - t : t;
+    const int n = g + ng * (tt / tpb), p0 = (tt % tpb) * PT;
+    const int grp0 = p0 >> ns_shift;
+    const float2 *eb = ent + ((size_t)n * groups + grp0) * CSP + cw * 64 + lane;
+    float2 e[2];
+#pragma unroll
+    for (int gi = 0; gi < 2; ++gi) e[gi] = gi < ngt ? eb[(size_t)gi * CSP] : make_float2(0.f, 0.f);
+    __syncthreads();                              // the tile is in b0; nobody reads b1 any more
+    const float *col = b0 + (kw * KPER) * PITCH;
+#pragma unroll
+    for (int gi = 0; gi < 2; ++gi) {
+      if (gi < ngt) {                             // (uniform)
+        // position of the entry relative to the tile; outside it (the other half of a 64-group): a zero
+        const int rel = __float_as_int(e[gi].y) + (((grp0 + gi) << ns_shift) - p0);
+        const bool in = rel >= 0 && rel < PT;
+        const float v = in ? e[gi].x : 0.f;
+        const int at = in ? rel : 0;
+#pragma unroll
+        for (int kk = 0; kk < KPER; ++kk) wacc[kk] = __builtin_fmaf(v, col[kk * PITCH + at], wacc[kk]);
+      }
+    }
+    write_tile(b1);
+    load_tile(t + 2 * nwg);
+    float *const tb = b0; b0 = b1; b1 = tb;
+  }
+  // partial[(g nwg + rank)][c][k]; tiled: [64 x 64 block][g nwg + rank][c % 64][k % 64]
+  const int c = cw * 64 + lane, k0 = kw * KPER;
+  float *wd = tiled ? partial + ((size_t)((c >> 6) * (K / 64) + (k0 >> 6)) * ng * nwg + (size_t)g * nwg + rank) * 4096 + (size_t)(c & 63) * 64
+                    : partial + (((size_t)g * nwg + rank) * CSP + c) * K + k0;
+#pragma unroll
+  for (int kk = 0; kk < KPER; kk += 4)
+    *(f32x4 *)(wd + kk) = (f32x4){wacc[kk], wacc[kk + 1], wacc[kk + 2], wacc[kk + 3]};
+}
+
 // dw[g][i] = sum over the nparts partials of group g, in a fixed order
 // (a launch covers the ci columns [col0, col0 + ci) of dw (ng, co, ld): wide layers run as column blocks)
 __global__ __launch_bounds__(1024) void pw_wgrad_reduce_kernel(int total, int nparts,
@@ -607,8 +712,21 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
                            size_t workspace_bytes, const float *bnz, const float *bnb, float *dz,
                            float *d_rb, int rb_group, hipStream_t s, bool defer = false,
                            const float *k4_w = nullptr, const float *fdg_w = nullptr, float *fdg_part = nullptr,
-                           float *fdg_gpart = nullptr) {
+                           float *fdg_gpart = nullptr, const float *sp_ent = nullptr, int sp_ns = 0) {
   NESIE_REQUIRE(nb >= 0 && ng >= 1 && co >= 1 && ci >= 1 && p >= 0 && dw, W);
+  // (sp_ent: dY is given as a max-pool's entries and the partials come from pw_wgrad_sparse_kernel)
+  NESIE_REQUIRE(!sp_ent || (co == 128 && ci == 256 && (sp_ns == 16 || sp_ns == 64) && p % sp_ns == 0 && x_coef && x_relu &&
+                            !bnb && !d_rb && !k4_w && ((uintptr_t)sp_ent & 7) == 0), W);
+  auto launch_sparse = [&](float *partial, int nwg, int rev, int tiled) {
+    const size_t lds = (size_t)2 * 256 * 36 * sizeof(float) + 256 * sizeof(float2);
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute((const void *)pw_wgrad_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr = true;
+    }
+    hipLaunchKernelGGL(pw_wgrad_sparse_kernel, dim3(nwg * ng), dim3(512), lds, s, nb, ng, p, x, x_bstride, x_coef,
+                       (const float2 *)sp_ent, sp_ns == 16 ? 4 : 6, (int)(p / sp_ns), partial, nwg, rev, tiled);
+  };
   // (k4_w: x is X4 (nb, 4, p) and the 64 operand rows are rebuilt from it -- one build)
   NESIE_REQUIRE(!k4_w || (co == 64 && ci == 64 && ng == 1 && bnb && x_coef && !d_rb && x_bstride >= 4 * p &&
                           ((uintptr_t)k4_w & 15) == 0), W);
@@ -621,7 +739,7 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
     set_error("%s: %d x %d over %lld positions is outside the built tiles", W, co, ci, p);
     return NESIE_ERR_UNSUPPORTED;
   }
-  NESIE_REQUIRE(nb % ng == 0 && dy && x && workspace, W);
+  NESIE_REQUIRE(nb % ng == 0 && (dy || sp_ent) && x && workspace, W);
   NESIE_REQUIRE(workspace_bytes >= nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p), W);
   NESIE_REQUIRE((((uintptr_t)dy | (uintptr_t)x) & 15) == 0 && (dy_bstride & 3) == 0 && (x_bstride & 3) == 0, W);
   NESIE_REQUIRE((long long)(co > ci ? co : ci) * p < (1ll << 30), W);
@@ -647,7 +765,8 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
                          (float *)nullptr, (float *)nullptr, 0, rev, (const float *)nullptr,            \
                          (const float *)nullptr, (float *)nullptr, (float *)nullptr);                   \
     } while (0)
-    if (x_coef) LT(true); else LT(false);
+    if (sp_ent) launch_sparse(partial, nwg, rev, 1);
+    else if (x_coef) LT(true); else LT(false);
 #undef LT
     if (defer) {
       if (g_pending.n == RD_MAX) { const int st = rd_flush(s); if (st) return st; }
@@ -713,7 +832,8 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
       hipLaunchKernelGGL(kern, dim3(nwg * ng), dim3(512), lds, s, nb, ng, co, cw, p, dy, dy_bstride, xc, x_bstride, cc,
                          ci, lo, partial, nwg, bnz, bnb, dz, d_rb, rb_group, rev, k4_w, (const float *)nullptr,
                          (float *)nullptr, (float *)nullptr);
-    } else if (co <= 64 && cw <= 64) L(4, 4, 2, 4);
+    } else if (sp_ent) launch_sparse(partial, nwg, rev, 0);      // (block == ci: one pass of this loop)
+    else if (co <= 64 && cw <= 64) L(4, 4, 2, 4);
     else if (co <= 128 && cw <= 64) L(8, 4, 4, 2);
     else if (co <= 128 && cw <= 128) L(8, 8, 2, 4);
     else if (co <= 128 && cw <= 192) L(8, 12, 2, 4);
@@ -754,6 +874,31 @@ extern "C" int nesie_pw_wgrad_deferred(int nb, int ng, int co, int ci, long long
                                        size_t workspace_bytes, void *stream) {
   return pw_wgrad_launch("pw_wgrad_deferred", nb, ng, co, ci, p, dy, dy_bstride, x, x_bstride, x_coef, x_relu, dw,
                          workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, true);
+}
+
+// nesie_pw_wgrad / _deferred for a dY that is a max-pool's gradient given as entries (pw_wgrad_sparse_kernel):
+// dw and every partial bit for bit what the dense launch over the expanded tensor leaves
+extern "C" int nesie_pw_wgrad_sparse_supported(int co, int ci, long long p, int ns) {
+  return co == 128 && ci == 256 && (ns == 16 || ns == 64) && p >= ns && p % ns == 0 && p % 32 == 0 &&
+                 (pw_wgrad_tiled(1, 1, co, ci, p) || nesie_pw_wgrad_supported(co, ci, p)) ? 1 : 0;
+}
+extern "C" int nesie_pw_wgrad_sparse(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
+                                     const float *x, long long x_bstride, const float *x_coef, float *dw,
+                                     void *workspace, size_t workspace_bytes, void *stream) {
+  const char *W = "pw_wgrad_sparse";
+  NESIE_REQUIRE(ent && nesie_pw_wgrad_sparse_supported(co, ci, p, ns), W);
+  return pw_wgrad_launch(W, nb, ng, co, ci, p, nullptr, 0, x, x_bstride, x_coef, 1, dw, workspace, workspace_bytes,
+                         nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, false, nullptr, nullptr, nullptr,
+                         nullptr, ent, ns);
+}
+extern "C" int nesie_pw_wgrad_sparse_deferred(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
+                                              const float *x, long long x_bstride, const float *x_coef, float *dw,
+                                              void *workspace, size_t workspace_bytes, void *stream) {
+  const char *W = "pw_wgrad_sparse_deferred";
+  NESIE_REQUIRE(ent && nesie_pw_wgrad_sparse_supported(co, ci, p, ns), W);
+  return pw_wgrad_launch(W, nb, ng, co, ci, p, nullptr, 0, x, x_bstride, x_coef, 1, dw, workspace, workspace_bytes,
+                         nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, true, nullptr, nullptr, nullptr,
+                         nullptr, ent, ns);
 }
 
 extern "C" int nesie_pw_wgrad_flush_deferred(void *stream) { return rd_flush((hipStream_t)stream); }

@@ -1312,6 +1312,61 @@ class HipKernels:
                     part_m, part_s, part_w, ms, dw)
         return da, part
 
+    # ---- a convolution pooled directly (MiniPointNet tail): backward from the entries -------------
+    def pool_tail_pack(self, g, argmax, pooled=None):
+        """g, argmax (uint8) (NB, C, M) -> ent (NB, M, C, 2) = (g -- masked by pooled > 0 when given
+        --, arg-max position as int bits) (nesie_pool_tail_pack)."""
+        _check(g, argmax); _f32(g)
+        nb, c, m = g.shape
+        assert argmax.dtype == torch.uint8 and tuple(argmax.shape) == (nb, c, m)
+        if pooled is not None:
+            _check(pooled); _f32(pooled)
+            assert tuple(pooled.shape) == (nb, c, m)
+        ent = torch.empty(nb, m, c, 2, dtype=torch.float32, device=g.device)
+        _launch("nesie_pool_tail_pack", g, nb, c, m, g, pooled, argmax, ent)
+        return ent
+
+    def pw_dgrad_bn_reduce_sparse(self, ent, ns, w, z, z_coef, da, ng=1):
+        """``pw_dgrad_bn_reduce`` whose dy (NB, 128, P) is given as the entries of a max over groups of
+        ``ns`` positions, ent (NB, P / ns, 128, 2) (nesie_pw_dgrad_bn_reduce_sparse): bit for bit the
+        dense launch's da and partials."""
+        _check(ent, z_coef); _f32(ent, w, z, da, z_coef)
+        nb, cout, p = z.shape
+        k = 128
+        assert tuple(ent.shape) == (nb, p // ns, k, 2) and p % ns == 0
+        assert w.dim() == 3 and w.shape[0] == ng and w.shape[1] == cout and w.shape[2] == k and nb % ng == 0
+        for t in (z, da):
+            assert t.is_cuda and t.stride(2) == 1 and t.stride(1) == p
+        assert tuple(da.shape) == (nb, cout, p) and tuple(z_coef.shape) == (ng * cout, 4)
+        part = torch.empty(ng * cout, self.pw_stat_slots(nb, ng, k, cout, p), 2,
+                           dtype=torch.float32, device=z.device)
+        bs = lambda t, rows: t.stride(0) if nb > 1 else rows * p  # noqa: E731
+        _launch("nesie_pw_dgrad_bn_reduce_sparse", z, nb, ng, k, cout, p, int(ns), ent, w,
+                w.stride(0) if ng > 1 else 0, w.stride(1), w.stride(2), da, bs(da, cout), z,
+                bs(z, cout), z_coef, part)
+        return part
+
+    def pw_wgrad_sparse_supported(self, co, ci, p, ns):
+        return bool(_lib.load().nesie_pw_wgrad_sparse_supported(int(co), int(ci), int(p), int(ns)))
+
+    def pw_wgrad_sparse(self, ent, ns, x, dw, ng=1, x_coef=None, final=False):
+        """``pw_wgrad`` whose dy (NB, 128, P) is given as the entries of a max over groups of ``ns``
+        positions, ent (NB, P / ns, 128, 2) (nesie_pw_wgrad_sparse): dw (ng, 128, ci) bit for bit the
+        dense launch's; x (NB, ci, P) raw, x_coef (ng*ci, 4) its folded BatchNorm (ReLU applied)."""
+        _check(ent, x_coef); _f32(ent, x, x_coef, dw)
+        nb, ci, p = x.shape
+        co = ent.shape[2]
+        assert tuple(ent.shape) == (nb, p // ns, co, 2) and p % ns == 0 and nb % ng == 0
+        assert x.is_cuda and x.stride(2) == 1 and x.stride(1) == p
+        assert dw.is_contiguous() and dw.numel() == ng * co * ci and tuple(x_coef.shape) == (ng * ci, 4)
+        need = _lib.load().nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
+        defer = final and HipKernels._deferred is not None
+        ws = _workspace(need, x.device)
+        _launch("nesie_pw_wgrad_sparse_deferred" if defer else "nesie_pw_wgrad_sparse", x, nb, ng, co, ci, p,
+                int(ns), ent, x, x.stride(0) if nb > 1 else ci * p, x_coef, dw, ws, need)
+        if defer:
+            HipKernels._deferred.append((ws, dw))
+
     def mlp_stat_finalize(self, part, count, gamma, beta, running_mean, running_var, momentum, eps,
                           coef, channel_major=False):
         """(parts, C, 2) -- or, channel_major, (C, parts, 2) -- unshifted (sum, sum of squares)

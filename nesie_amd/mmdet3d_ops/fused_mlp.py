@@ -699,16 +699,28 @@ class MiniTailFn(Function):
         B, S, half, P = c.shape
         H2, F = wl.shape[1], w4.shape[1]
         G = ctx.G
-        # gradient of the last conv's output: the pooled gradient at the arg-max, zero elsewhere
-        dz = c.new_empty(B, S, F, P // G, G)
-        backend.group_max_pool_backward(dout.contiguous(), arg, dz)
-        dzf = dz.view(B * S, F, P)
         yf = y.view(B * S, H2, P)
         dw4 = None
-        if ctx.needs_input_grad[7]:
-            dw4 = _wgrad(backend, dzf, yf, coef1, ng=S, slot=ctx.slots[2])
         da = c.new_empty(B * S, H2, P)
-        part = backend.pw_dgrad_bn_reduce(dzf, w4.transpose(1, 2), yf, coef1, da, ng=S)
+        if mini_tail_sparse_supported(backend, F, H2, G, P):
+            # No norm and no ReLU between conv4 and the max: the gradient of its output is ONE non-zero
+            # per (channel, group) -- kept as entries (value, position); the dense (B S, F, P) tensor
+            # is never formed.  The input gradient builds its operand rows from them (bit for bit the
+            # dense launch's result), the weight gradient is a sparse product on the vector ALUs that
+            # leaves the dense launch's partials (bit for bit its dW4, deferred reduction included).
+            ent = backend.pool_tail_pack(dout.contiguous().view(B * S, F, P // G), arg.view(B * S, F, P // G))
+            if ctx.needs_input_grad[7]:
+                dw4 = _dst(ctx.slots[2], c, S, F, H2)
+                backend.pw_wgrad_sparse(ent, G, yf, dw4, ng=S, x_coef=coef1, final=ctx.slots[2] is not None)
+            part = backend.pw_dgrad_bn_reduce_sparse(ent, G, w4.transpose(1, 2), yf, coef1, da, ng=S)
+        else:
+            # gradient of the last conv's output: the pooled gradient at the arg-max, zero elsewhere
+            dz = c.new_empty(B, S, F, P // G, G)
+            backend.group_max_pool_backward(dout.contiguous(), arg, dz)
+            dzf = dz.view(B * S, F, P)
+            if ctx.needs_input_grad[7]:
+                dw4 = _wgrad(backend, dzf, yf, coef1, ng=S, slot=ctx.slots[2])
+            part = backend.pw_dgrad_bn_reduce(dzf, w4.transpose(1, 2), yf, coef1, da, ng=S)
         dgamma, dbeta = _dst(ctx.slots[0], c, S * H2), _dst(ctx.slots[1], c, S * H2)
         cf = c.view(B * S, half, P)
         dwl = None
@@ -733,6 +745,17 @@ class MiniTailFn(Function):
         backend.pw_layer_forward(dyf, wl.transpose(1, 2), ng=S, y=dc.view(B * S, half, P))
         setattr(dc, _OWNED_MARK, True)      # nobody else holds this gradient buffer
         return dc, dsmall, None, None, dwl, dgamma, dbeta, dw4
+
+
+# Tests flip this to obtain the dense backward of the MiniPointNet tail on the same inputs.
+MINI_TAIL_SPARSE = True
+
+
+def mini_tail_sparse_supported(backend, F, H2, G, P):
+    """The MiniPointNet tail's backward runs from the max-pool's entries (no dense gradient of conv4's
+    output) at the built shape: F = 128, H2 = 256, G in {16, 64}, whole 64-position tiles."""
+    return (MINI_TAIL_SPARSE and backend.name == 'hip' and F == 128 and H2 == 256 and G in (16, 64)
+            and P % 64 == 0 and backend.pw_wgrad_sparse_supported(F, H2, P, G))
 
 
 def mini_pointnets_fused_supported(backend, c0, c0_part, G):

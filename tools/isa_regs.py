@@ -1,4 +1,5 @@
-"""Register / LDS / occupancy table of the layer-kernel instantiations (pw_fwd_kernel, pw_wgrad_kernel):
+"""Register / LDS / occupancy table of the layer-kernel instantiations (pw_fwd_kernel, pw_wgrad_kernel) and
+the streaming kernels pt_gram_kernel and pw_wgrad_sparse_kernel (static LDS only -- theirs is dynamic):
 compiles each translation unit to gfx950 assembly and reads the kernel descriptors' metadata.
     .vgpr_count -> allocation (granule 8) -> waves per SIMD (MI355X_MICROARCH.md, register files)
     workgroups per CU = min(waves-per-SIMD * 4 / waves-per-workgroup, 160 KB / LDS per workgroup)
@@ -59,7 +60,7 @@ def main():
     for path, rows in zip(files, results):
         print('==', os.path.relpath(path, ROOT))
         for r in sorted(rows, key=lambda r: r['name']):
-            if 'pw_fwd_kernel' not in r['name'] and 'pw_wgrad_kernel' not in r['name']:
+            if not any(k in r['name'] for k in ('pw_fwd_kernel', 'pw_wgrad_kernel', 'pt_gram_kernel', 'pw_wgrad_sparse_kernel')):
                 continue
             w, alloc = waves_per_simd(r['vgpr'])
             wpw = max(r['wg'] // 64, 1)
