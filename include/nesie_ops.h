@@ -597,16 +597,12 @@ int nesie_pw_stats_finalize(int channels, int cout, int nslots, const float *sta
 /* Pooling tail: combine the group / pool_group partial extrema of every group of `group`
  * positions; with coef (this layer's BatchNorm) the value is relu?(scale * ext + bias) of the
  * extremum the sign of the scale selects (= max over the group of the normalised activation).
- * pooled (nb, channels, p / group), argmax the position inside the group (first on ties). */
+ * pooled (nb, channels, p / group), argmax the position inside the group (first on ties);
+ * zstar (NULL = skip), like pooled: the raw extremum each pooled value came from. */
 int nesie_pw_pool_finish(int nb, int ng, int channels, long long p, int group, int pool_group,
                          const float *pmax, const float *pmin, const uint8_t *amax,
                          const uint8_t *amin, const float *coef, int relu, float *pooled,
-                         uint8_t *argmax, void *stream);
-/* ... also leaving the raw extremum each pooled value came from, zstar (nb, channels, p / group). */
-int nesie_pw_pool_finish_z(int nb, int ng, int channels, long long p, int group, int pool_group,
-                           const float *pmax, const float *pmin, const uint8_t *amax,
-                           const uint8_t *amin, const float *coef, int relu, float *pooled,
-                           uint8_t *argmax, float *zstar, void *stream);
+                         uint8_t *argmax, float *zstar, void *stream);
 
 /* Backward of a POOLED TAIL -- last 1x1 conv (k -> c, bias-free) + training-mode BatchNorm + ReLU +
  * max over the ns samples of every group (PointSAModule's shared MLP and _pool_features,
@@ -653,11 +649,11 @@ int nesie_pool_tail_wgrad(int nb, int k, int c, long long p, int ns, const float
  * nesie_pw_dgrad_bn_reduce_sparse: nesie_pw_dgrad_bn_reduce with x given as ent (c = 128, ns in
  *   {16, 32, 64}, p % 64 == 0): the same launch parameters, y and bn_part bit for bit the dense
  *   launch's; nslots = nesie_pw_stat_slots(nb, ng, 128, cout, p).
- * nesie_pw_wgrad_sparse / _deferred: nesie_pw_wgrad / nesie_pw_wgrad_deferred (below) with dy given as ent
+ * nesie_pw_wgrad_sparse: nesie_pw_wgrad (below) with dy given as ent
  *   (co = 128, ci = 256, ns in {16, 64}; x_coef required, act = relu): a sparse product on the vector
  *   ALUs, one pass over x, that walks the dense launch's tiles and leaves the dense launch's partials --
  *   dw is bit for bit what nesie_pw_wgrad computes from the expanded tensor; same workspace size
- *   (nesie_pw_wgrad_workspace_bytes), same reduction, same rules for a deferred one. */
+ *   (nesie_pw_wgrad_workspace_bytes), same reduction, same `defer`. */
 int nesie_pool_tail_pack(int nb, int c, int m, const float *grad_pooled, const float *pooled,
                          const uint8_t *argmax, float *ent, void *stream);
 int nesie_pw_dgrad_bn_reduce_sparse(int nb, int ng, int c, int cout, long long p, int ns,
@@ -668,11 +664,7 @@ int nesie_pw_dgrad_bn_reduce_sparse(int nb, int ng, int c, int cout, long long p
 int nesie_pw_wgrad_sparse_supported(int co, int ci, long long p, int ns);
 int nesie_pw_wgrad_sparse(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
                           const float *x, long long x_bstride, const float *x_coef, float *dw,
-                          void *workspace, size_t workspace_bytes, void *stream);
-int nesie_pw_wgrad_sparse_deferred(int nb, int ng, int co, int ci, long long p, int ns,
-                                   const float *ent, const float *x, long long x_bstride,
-                                   const float *x_coef, float *dw, void *workspace,
-                                   size_t workspace_bytes, void *stream);
+                          void *workspace, size_t workspace_bytes, int defer, void *stream);
 
 /* Weight gradient of the same layers: dw[g][co][ci] = sum over the batches n of group g (n % ng
  * == g) and all positions of dy[n][co][pos] * act(x[n][ci][pos]), act as in
@@ -685,27 +677,26 @@ int nesie_pw_wgrad_sparse_deferred(int nb, int ng, int co, int ci, long long p, 
  * launch each -- or, when the position count is small (nesie_pw_wgrad_tiled: the 1-D chains,
  * 256 x 512 over 8 x 1024 positions), as ONE launch over 64 x 64 blocks of the product, every
  * block with its own runs of positions (split-K with a fixed-order reduction).
- * workspace = nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p). */
+ * workspace = nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p); defer: see "Deferred reductions". */
 int nesie_pw_wgrad_supported(int co, int ci, long long p);
 int nesie_pw_wgrad_tiled(int nb, int ng, int co, int ci, long long p);
 size_t nesie_pw_wgrad_workspace_bytes(int nb, int ng, int co, int ci, long long p);
 int nesie_pw_wgrad(int nb, int ng, int co, int ci, long long p, const float *dy,
                    long long dy_bstride, const float *x, long long x_bstride,
                    const float *x_coef, int x_relu, float *dw, void *workspace,
-                   size_t workspace_bytes, void *stream);
+                   size_t workspace_bytes, int defer, void *stream);
 
 /* Deferred reductions: nothing in a backward pass reads a weight gradient (its consumers are the
- * optimiser and the gradient all-reduce), so the *_deferred forms run the product only and leave the
- * fixed-order addition of the per-workgroup partials PENDING; nesie_pw_wgrad_flush_deferred(stream)
+ * optimiser and the gradient all-reduce), so every weight-gradient entry point (nesie_pw_wgrad,
+ * nesie_pw_wgrad_sparse, nesie_pw_wgrad_bn_backward and its _k4 / _k4_fused forms) takes `defer`:
+ * 0 reduces at once; anything else runs the product only and leaves the fixed-order addition of the
+ * per-workgroup partials PENDING (whatever else the launch writes -- dz, dgamma, dbeta, the input
+ * gradient's reductions -- is complete on return).  nesie_pw_wgrad_flush_deferred(stream)
  * then finishes every pending gradient in ONE launch (descriptor table in the kernel arguments;
- * each element is summed exactly as by the immediate forms: bit-identical).  Until the flush the
+ * each element is summed exactly as by an immediate launch: bit-identical).  Until the flush the
  * workspace of a deferred launch must stay untouched and dw holds no valid data.  A launch that
  * runs as several column blocks reduces immediately.  nesie_pw_wgrad_pending(): how many wait;
  * nesie_pw_wgrad_drop_deferred(): forget them (error paths).  Host-side queue, one per process. */
-int nesie_pw_wgrad_deferred(int nb, int ng, int co, int ci, long long p, const float *dy,
-                            long long dy_bstride, const float *x, long long x_bstride,
-                            const float *x_coef, int x_relu, float *dw, void *workspace,
-                            size_t workspace_bytes, void *stream);
 int nesie_pw_wgrad_flush_deferred(void *stream);
 int nesie_pw_wgrad_pending(void);
 int nesie_pw_wgrad_drop_deferred(void);
@@ -731,15 +722,7 @@ int nesie_pw_wgrad_bn_backward(int nb, int ng, int co, int ci, long long p, cons
                                long long x_bstride, const float *x_coef, int x_relu, float *dz,
                                float *dw, float *dgamma, float *dbeta, float *coef_ws,
                                float *d_row_bias, int rb_group, void *workspace,
-                               size_t workspace_bytes, void *stream);
-/* ... with the weight gradient's reduction left pending (dz, dgamma, dbeta complete on return). */
-int nesie_pw_wgrad_bn_backward_deferred(int nb, int ng, int co, int ci, long long p, const float *da,
-                               const float *z, long long z_bstride, const float *z_coef,
-                               const float *gamma, const float *part, int nslots, const float *x,
-                               long long x_bstride, const float *x_coef, int x_relu, float *dz,
-                               float *dw, float *dgamma, float *dbeta, float *coef_ws,
-                               float *d_row_bias, int rb_group, void *workspace,
-                               size_t workspace_bytes, void *stream);
+                               size_t workspace_bytes, int defer, void *stream);
 
 /* The layer kernel for skinny HBM-bound first layers (cin <= 64, cout <= 128): W stays in
  * LDS / registers and every wave streams its own 32-position columns straight from global
@@ -776,7 +759,7 @@ int nesie_mlp_layer_forward_stream(int b, int cin, int cout, long long p, const 
  *    row-major; in_coef [64][4] the first layer's folded norm), with statistics like
  *    nesie_pw_layer_forward;
  *  - nesie_pw_wgrad_bn_backward_k4: nesie_pw_wgrad_bn_backward of the second layer (64 x 64) with
- *    its X operand rebuilt (x_coef = in_coef above); defer != 0 leaves the reduction pending;
+ *    its X operand rebuilt (x_coef = in_coef above);
  *  - nesie_pw_dgrad_bn_reduce_k4: nesie_pw_dgrad_bn_reduce of the second layer whose OUTPUT (the
  *    gradient of the first activation) is not stored: bn_part as there, and
  *    g_part[(m * nslots + slot)][4] = sum over the slot's positions of gg[m] X4[j], j = 0 .. 3

@@ -32,7 +32,7 @@ int walk_dir(long long operand_bytes) {
 }
 }  // namespace nesie
 
-extern "C" int nesie_abi_version(void) { return 1; }
+extern "C" int nesie_abi_version(void) { return 2; }
 extern "C" int nesie_set_distance_form(int form) {
   NESIE_REQUIRE(form >= 0 && form <= 2, "set_distance_form");
   nesie::g_distance_form = form;

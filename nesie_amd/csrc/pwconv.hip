@@ -193,76 +193,64 @@ PW_GEOM_DEF(8, 2, 8, 1, 1)
 PW_GEOM_DEF(8, 1, 8, 1, 1)
 #endif
 
-static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long long p,
-                           const float *x, long long x_bstride, const float *w,
-                           long long w_gstride, int w_rstride, int w_cstride,
-                           const float *in_coef, int in_relu, const float *row_bias,
-                           int rb_group, const float *bias, float *y,
-                           long long y_bstride, float *stat_part, int pool_group,
-                           int pool_min, float *pool_max_out, float *pool_min_out,
-                           uint8_t *arg_max_out, uint8_t *arg_min_out, const float *bn_z,
-                           long long bnz_bstride, const float *bn_coef, float *bn_part,
-                           void *stream, const float *k4_w = nullptr, int k4_in = 0,
-                           float *k4_gpart = nullptr, const float *sp_ent = nullptr, int sp_ns = 0) {
+// What a launch of the layer kernel needs beside its kernel argument: the settings PwFwd holds only
+// in derived form (a clamp, a shift) or not at all.  An entry point value-initialises a PwFwd and a
+// PwHost, fills the fields it uses by name, and pw_forward_impl validates, derives the rest and launches.
+struct PwHost { int in_relu, rb_group, pool_group, pool_min, k4_in, sp_ns; };
+
+static int pw_forward_impl(const char *W, PwFwd a, const PwHost &h, void *stream) {
+  const int nb = a.nb, ng = a.ng, k = a.k, cout = a.cout;
+  const long long p = a.p;
   NESIE_REQUIRE(nb >= 0 && ng >= 1 && k >= 1 && cout >= 1 && p >= 0, W);
   if (nb == 0 || p == 0) return NESIE_OK;
-  NESIE_REQUIRE(nb % ng == 0 && (x || sp_ent) && w, W);
+  NESIE_REQUIRE(nb % ng == 0 && (a.x || a.sp_ent) && a.w, W);
   PwGeom g;
   if (!pw_geometry(k, cout, &g) || p % g.pt != 0 || (long long)(k > cout ? k : cout) * p >= (1ll << 30)) {
     set_error("%s: %d -> %d over %lld positions is outside the built tiles", W, k, cout, p);
     return NESIE_ERR_UNSUPPORTED;
   }
-  NESIE_REQUIRE(((uintptr_t)x & 15) == 0 && (x_bstride & 3) == 0, W);
-  NESIE_REQUIRE(!y || (((uintptr_t)y & 15) == 0 && (y_bstride & 3) == 0), W);
+  NESIE_REQUIRE(((uintptr_t)a.x & 15) == 0 && (a.x_bs & 3) == 0, W);
+  NESIE_REQUIRE(!a.y || (((uintptr_t)a.y & 15) == 0 && (a.y_bs & 3) == 0), W);
   int epi = 0, pg = 16;
-  if (in_coef) epi |= PW_AFFINE;
-  if (y) epi |= PW_STORE;
-  if (stat_part) epi |= PW_STATS;
-  if (row_bias) {
-    NESIE_REQUIRE(rb_group >= 16 && (rb_group & (rb_group - 1)) == 0 && p % rb_group == 0, W);
+  if (a.in_coef) epi |= PW_AFFINE;
+  if (a.y) epi |= PW_STORE;
+  if (a.stat_part) epi |= PW_STATS;
+  if (a.row_bias) {
+    NESIE_REQUIRE(h.rb_group >= 16 && (h.rb_group & (h.rb_group - 1)) == 0 && p % h.rb_group == 0, W);
     epi |= PW_ROWBIAS;
   }
-  if (bias) epi |= PW_BIAS;
-  if (bn_z) {
-    NESIE_REQUIRE((y || k4_gpart) && bn_coef && bn_part && ((uintptr_t)bn_z & 15) == 0 && (bnz_bstride & 3) == 0, W);
+  if (a.bias) epi |= PW_BIAS;
+  if (a.bn_z) {
+    NESIE_REQUIRE((a.y || a.k4_gpart) && a.bn_coef && a.bn_part && ((uintptr_t)a.bn_z & 15) == 0 && (a.bnz_bs & 3) == 0, W);
     epi |= PW_BNRED;
   }
-  if (k4_in) {      // the operand is rebuilt from the four rows of x (pwconv_fwd.h, PW_K4IN)
-    NESIE_REQUIRE(k4_w && in_coef && k == 64 && ng == 1 && x_bstride >= 4 * p && ((uintptr_t)k4_w & 15) == 0, W);
+  if (h.k4_in) {    // the operand is rebuilt from the four rows of x (pwconv_fwd.h, PW_K4IN)
+    NESIE_REQUIRE(a.k4_w && a.in_coef && k == 64 && ng == 1 && a.x_bs >= 4 * p && ((uintptr_t)a.k4_w & 15) == 0, W);
     epi |= PW_K4IN;
   }
-  if (k4_gpart) {   // Z of the reduction is rebuilt from the four rows of bn_z (PW_K4Z)
-    NESIE_REQUIRE(k4_w && bn_z && !y && cout == 64 && ng == 1 && bnz_bstride >= 4 * p && ((uintptr_t)k4_w & 15) == 0 &&
-                  ((uintptr_t)k4_gpart & 15) == 0, W);
+  if (a.k4_gpart) { // Z of the reduction is rebuilt from the four rows of bn_z (PW_K4Z)
+    NESIE_REQUIRE(a.k4_w && a.bn_z && !a.y && cout == 64 && ng == 1 && a.bnz_bs >= 4 * p && ((uintptr_t)a.k4_w & 15) == 0 &&
+                  ((uintptr_t)a.k4_gpart & 15) == 0, W);
     epi |= PW_K4Z;
   }
-  if (pool_group) {
-    NESIE_REQUIRE(pool_group == 16 || pool_group == 32, W);
-    NESIE_REQUIRE(pool_max_out && arg_max_out && p % pool_group == 0, W);
-    NESIE_REQUIRE(!pool_min || (pool_min_out && arg_min_out), W);
-    epi |= PW_POOL | (pool_min ? PW_POOLMIN : 0);
-    pg = pool_group;
+  if (h.pool_group) {
+    NESIE_REQUIRE(h.pool_group == 16 || h.pool_group == 32, W);
+    NESIE_REQUIRE(a.pool_max && a.arg_max && p % h.pool_group == 0, W);
+    NESIE_REQUIRE(!h.pool_min || (a.pool_min && a.arg_min), W);
+    epi |= PW_POOL | (h.pool_min ? PW_POOLMIN : 0);
+    pg = h.pool_group;
   }
-  if (sp_ent) {     // every operand row is built from the entries (PW_SPARSE128 with SPC == K): no x
-    NESIE_REQUIRE(k == 128 && cout % 128 == 0 && epi == (PW_STORE | PW_BNRED) && ((uintptr_t)sp_ent & 7) == 0, W);
-    NESIE_REQUIRE((sp_ns == 16 || sp_ns == 32 || sp_ns == 64) && p % 64 == 0, W);
+  if (a.sp_ent) {   // every operand row is built from the entries (PW_SPARSE128 with SPC == K): no x
+    NESIE_REQUIRE(k == 128 && cout % 128 == 0 && epi == (PW_STORE | PW_BNRED) && ((uintptr_t)a.sp_ent & 7) == 0, W);
+    NESIE_REQUIRE((h.sp_ns == 16 || h.sp_ns == 32 || h.sp_ns == 64) && p % 64 == 0, W);
   }
-  PwFwd a;
-  a.sp_ent = (const float2 *)sp_ent; a.sp_ns_shift = sp_ent ? __builtin_ctz((unsigned)sp_ns) : 0;
-  a.sp_groups = sp_ent ? (int)(p / sp_ns) : 0;
-  a.x = x; a.x_bs = x_bstride; a.p = p; a.nb = nb; a.k = k;
-  a.w = w; a.w_gs = w_gstride; a.w_rs = w_rstride; a.w_cs = w_cstride; a.ng = ng; a.cout = cout;
-  a.in_coef = in_coef; a.in_lo = in_relu ? 0.f : -__builtin_inff();
-  a.y = y; a.y_bs = y_bstride;
-  a.row_bias = row_bias; a.rb_shift = row_bias ? __builtin_ctz((unsigned)rb_group) : 0;
-  a.bias = bias;
-  a.stat_part = stat_part;
-  a.pool_max = pool_max_out; a.pool_min = pool_min_out; a.arg_max = arg_max_out; a.arg_min = arg_min_out;
-  a.bn_z = bn_z; a.bnz_bs = bnz_bstride; a.bn_coef = bn_coef; a.bn_part = bn_part;
-  a.stamps = nullptr;
-  a.k4_w = k4_w; a.k4_gpart = k4_gpart;
+  // the derived fields of the kernel argument
+  a.sp_ns_shift = a.sp_ent ? __builtin_ctz((unsigned)h.sp_ns) : 0;
+  a.sp_groups = a.sp_ent ? (int)(p / h.sp_ns) : 0;
+  a.in_lo = h.in_relu ? 0.f : -__builtin_inff();
+  a.rb_shift = a.row_bias ? __builtin_ctz((unsigned)h.rb_group) : 0;
   a.w_stage = 1;
-  a.rev = walk_dir((long long)nb * (k4_in ? 4 : k) * p * 4);     // (a big operand is read last tile first: nesie_lib.hip)
+  a.rev = walk_dir((long long)nb * (h.k4_in ? 4 : k) * p * 4);   // (a big operand is read last tile first: nesie_lib.hip)
 #ifdef PW_STAMP
   a.stamps = g_pw_stamps;
 #endif
@@ -273,7 +261,7 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
   const int grid = a.nwg_g * ng * g.nhalf;
   static const bool xcd_on = !(getenv("NESIE_PW_XCD") && atoi(getenv("NESIE_PW_XCD")) == 0);   // A/B switch
   a.xcd_map = (xcd_on && g.nhalf > 1 && grid % (8 * g.nhalf) == 0) ? 1 : 0;
-  const size_t lds = pw_lds_bytes(g) + (k4_gpart ? 2048 : 0);    // (PW_K4Z: + the tile's X4, two halves)
+  const size_t lds = pw_lds_bytes(g) + (a.k4_gpart ? 2048 : 0);  // (PW_K4Z: + the tile's X4, two halves)
   hipStream_t s = (hipStream_t)stream;
   int st = NESIE_ERR_UNSUPPORTED;
 #define G(KT16, KH, WR, WC, RW)                                                          \
@@ -282,7 +270,7 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
 #ifdef PW_DEV
   G(8, 2, 8, 1, 1); G(8, 1, 8, 1, 1);
 #else
-  if (sp_ent) {
+  if (a.sp_ent) {
     st = pw_launch_sparse_8_1_8_1_1(a, grid, lds, s);
   } else {
     G(4, 1, 4, 1, 1); G(4, 1, 4, 1, 2); G(8, 1, 4, 1, 1); G(8, 1, 8, 1, 1);
@@ -298,6 +286,15 @@ static int pw_forward_impl(const char *W, int nb, int ng, int k, int cout, long 
   return check_launch(W);
 }
 
+// the fields every entry point sets: the problem, the operand and the weight view
+static PwFwd pw_problem(int nb, int ng, int k, int cout, long long p, const float *x, long long x_bstride,
+                        const float *w) {
+  PwFwd a{};
+  a.nb = nb; a.ng = ng; a.k = k; a.cout = cout; a.p = p;
+  a.x = x; a.x_bs = x_bstride; a.w = w;
+  return a;
+}
+
 extern "C" int nesie_pw_layer_forward(int nb, int ng, int k, int cout, long long p,
                                       const float *x, long long x_bstride, const float *w,
                                       long long w_gstride, int w_rstride, int w_cstride,
@@ -306,10 +303,14 @@ extern "C" int nesie_pw_layer_forward(int nb, int ng, int k, int cout, long long
                                       long long y_bstride, float *stat_part, int pool_group,
                                       int pool_min, float *pool_max_out, float *pool_min_out,
                                       uint8_t *arg_max_out, uint8_t *arg_min_out, void *stream) {
-  return pw_forward_impl("pw_layer_forward", nb, ng, k, cout, p, x, x_bstride, w, w_gstride,
-                         w_rstride, w_cstride, in_coef, in_relu, row_bias, rb_group, bias, y,
-                         y_bstride, stat_part, pool_group, pool_min, pool_max_out, pool_min_out,
-                         arg_max_out, arg_min_out, nullptr, 0, nullptr, nullptr, stream);
+  PwFwd a = pw_problem(nb, ng, k, cout, p, x, x_bstride, w);
+  a.w_gs = w_gstride; a.w_rs = w_rstride; a.w_cs = w_cstride;
+  a.in_coef = in_coef; a.row_bias = row_bias; a.bias = bias;
+  a.y = y; a.y_bs = y_bstride; a.stat_part = stat_part;
+  a.pool_max = pool_max_out; a.pool_min = pool_min_out; a.arg_max = arg_max_out; a.arg_min = arg_min_out;
+  PwHost h{};
+  h.in_relu = in_relu; h.rb_group = rb_group; h.pool_group = pool_group; h.pool_min = pool_min;
+  return pw_forward_impl("pw_layer_forward", a, h, stream);
 }
 
 // Input gradient of a layer, Y[n] = W[n % ng] . X[n] with W the transposed weight view, whose
@@ -325,9 +326,11 @@ extern "C" int nesie_pw_dgrad_bn_reduce(int nb, int ng, int k, int cout, long lo
                                         float *bn_part, void *stream) {
   const char *W = "pw_dgrad_bn_reduce";
   NESIE_REQUIRE(y && bn_z && bn_coef && bn_part, W);
-  return pw_forward_impl(W, nb, ng, k, cout, p, x, x_bstride, w, w_gstride, w_rstride, w_cstride,
-                         nullptr, 0, nullptr, 0, nullptr, y, y_bstride, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, nullptr, bn_z, bnz_bstride, bn_coef, bn_part, stream);
+  PwFwd a = pw_problem(nb, ng, k, cout, p, x, x_bstride, w);
+  a.w_gs = w_gstride; a.w_rs = w_rstride; a.w_cs = w_cstride;
+  a.y = y; a.y_bs = y_bstride;
+  a.bn_z = bn_z; a.bnz_bs = bnz_bstride; a.bn_coef = bn_coef; a.bn_part = bn_part;
+  return pw_forward_impl(W, a, PwHost{}, stream);
 }
 
 // nesie_pw_dgrad_bn_reduce for an x that is the gradient a max over groups of ns positions hands
@@ -345,10 +348,14 @@ extern "C" int nesie_pw_dgrad_bn_reduce_sparse(int nb, int ng, int c, int cout, 
                                                float *bn_part, void *stream) {
   const char *W = "pw_dgrad_bn_reduce_sparse";
   NESIE_REQUIRE(ent && y && bn_z && bn_coef && bn_part && c == 128, W);
-  return pw_forward_impl(W, nb, ng, c, cout, p, nullptr, 0, w, w_gstride, w_rstride, w_cstride,
-                         nullptr, 0, nullptr, 0, nullptr, y, y_bstride, nullptr, 0, 0, nullptr,
-                         nullptr, nullptr, nullptr, bn_z, bnz_bstride, bn_coef, bn_part, stream,
-                         nullptr, 0, nullptr, ent, ns);
+  PwFwd a = pw_problem(nb, ng, c, cout, p, nullptr, 0, w);
+  a.w_gs = w_gstride; a.w_rs = w_rstride; a.w_cs = w_cstride;
+  a.y = y; a.y_bs = y_bstride;
+  a.bn_z = bn_z; a.bnz_bs = bnz_bstride; a.bn_coef = bn_coef; a.bn_part = bn_part;
+  a.sp_ent = (const float2 *)ent;
+  PwHost h{};
+  h.sp_ns = ns;
+  return pw_forward_impl(W, a, h, stream);
 }
 
 // SA1's second layer over the REBUILT output of its first: the operand rows are relu(bn(W0 . X4)),
@@ -359,9 +366,13 @@ extern "C" int nesie_pw_layer_forward_k4(int nb, int cout, long long p, const fl
                                          int w_rstride, int w_cstride, const float *in_coef,
                                          float *y, long long y_bstride, float *stat_part,
                                          void *stream) {
-  return pw_forward_impl("pw_layer_forward_k4", nb, 1, 64, cout, p, x4, x4_bstride, w, 0, w_rstride,
-                         w_cstride, in_coef, 1, nullptr, 0, nullptr, y, y_bstride, stat_part, 0, 0,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, stream, w0, 1);
+  PwFwd a = pw_problem(nb, 1, 64, cout, p, x4, x4_bstride, w);
+  a.w_rs = w_rstride; a.w_cs = w_cstride;
+  a.in_coef = in_coef; a.k4_w = w0;
+  a.y = y; a.y_bs = y_bstride; a.stat_part = stat_part;
+  PwHost h{};
+  h.in_relu = 1; h.k4_in = 1;
+  return pw_forward_impl("pw_layer_forward_k4", a, h, stream);
 }
 
 // ... and the input gradient of that second layer, of which only the REDUCTIONS are wanted: the
@@ -376,9 +387,11 @@ extern "C" int nesie_pw_dgrad_bn_reduce_k4(int nb, int k, long long p, const flo
                                            float *g_part, void *stream) {
   const char *W = "pw_dgrad_bn_reduce_k4";
   NESIE_REQUIRE(x4 && w0 && bn_coef && bn_part && g_part, W);
-  return pw_forward_impl(W, nb, 1, k, 64, p, x, x_bstride, w, 0, w_rstride, w_cstride, nullptr, 0,
-                         nullptr, 0, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                         nullptr, x4, x4_bstride, bn_coef, bn_part, stream, w0, 0, g_part);
+  PwFwd a = pw_problem(nb, 1, k, 64, p, x, x_bstride, w);
+  a.w_rs = w_rstride; a.w_cs = w_cstride;
+  a.bn_z = x4; a.bnz_bs = x4_bstride; a.bn_coef = bn_coef; a.bn_part = bn_part;
+  a.k4_w = w0; a.k4_gpart = g_part;
+  return pw_forward_impl(W, a, PwHost{}, stream);
 }
 
 extern "C" int nesie_pw_stats_finalize(int channels, int cout, int nslots, const float *stat_part,
@@ -395,10 +408,11 @@ extern "C" int nesie_pw_stats_finalize(int channels, int cout, int nslots, const
   return check_launch(W);
 }
 
-static int pw_pool_finish_impl(int nb, int ng, int channels, long long p, int group, int pool_group,
-                               const float *pmax, const float *pmin, const uint8_t *amax,
-                               const uint8_t *amin, const float *coef, int relu,
-                               float *pooled, uint8_t *argmax, float *zstar, void *stream) {
+// zstar (NULL = skip): the raw extremum each pooled value came from (nb, channels, p / group)
+extern "C" int nesie_pw_pool_finish(int nb, int ng, int channels, long long p, int group, int pool_group,
+                                    const float *pmax, const float *pmin, const uint8_t *amax,
+                                    const uint8_t *amin, const float *coef, int relu,
+                                    float *pooled, uint8_t *argmax, float *zstar, void *stream) {
   const char *W = "pw_pool_finish";
   NESIE_REQUIRE(nb >= 0 && ng >= 1 && channels >= 1 && p >= 0 && group >= 1, W);
   if (nb == 0 || p == 0) return NESIE_OK;
@@ -409,22 +423,4 @@ static int pw_pool_finish_impl(int nb, int ng, int channels, long long p, int gr
                      total, channels, ng, (int)(p / group), group / pool_group, pool_group, pmax, pmin,
                      amax, amin, coef, relu ? 0.f : -__builtin_inff(), pooled, argmax, zstar);
   return check_launch(W);
-}
-
-extern "C" int nesie_pw_pool_finish(int nb, int ng, int channels, long long p, int group, int pool_group,
-                                    const float *pmax, const float *pmin, const uint8_t *amax,
-                                    const uint8_t *amin, const float *coef, int relu,
-                                    float *pooled, uint8_t *argmax, void *stream) {
-  return pw_pool_finish_impl(nb, ng, channels, p, group, pool_group, pmax, pmin, amax, amin, coef, relu,
-                             pooled, argmax, nullptr, stream);
-}
-
-// ... and the raw extremum each pooled value came from (nb, channels, p / group)
-extern "C" int nesie_pw_pool_finish_z(int nb, int ng, int channels, long long p, int group, int pool_group,
-                                      const float *pmax, const float *pmin, const uint8_t *amax,
-                                      const uint8_t *amin, const float *coef, int relu,
-                                      float *pooled, uint8_t *argmax, float *zstar, void *stream) {
-  NESIE_REQUIRE(zstar, "pw_pool_finish_z");
-  return pw_pool_finish_impl(nb, ng, channels, p, group, pool_group, pmax, pmin, amax, amin, coef, relu,
-                             pooled, argmax, zstar, stream);
 }

@@ -513,7 +513,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_reduce_tiled_kernel(int co, int 
 // ---- deferred reductions (round 5) ------------------------------------------------------------
 // The partials of a weight gradient are consumed by nobody but the optimiser (and the gradient
 // all-reduce): nothing in the backward pass reads dW.  So a launch may leave its reduction PENDING
-// (nesie_pw_wgrad_deferred / nesie_pw_wgrad_bn_backward_deferred: the workspace then has to stay
+// (`defer` != 0 in the weight-gradient entry points: the workspace then has to stay
 // alive) and nesie_pw_wgrad_flush_deferred adds the partials of every pending gradient in ONE launch
 // -- a descriptor table in the kernel arguments, a workgroup finds its descriptor from the block
 // index -- with each element summed exactly as its own reduce kernel sums it (bit-identical).  39
@@ -706,133 +706,130 @@ __global__ __launch_bounds__(64) void pw_bnb_coef_kernel(int channels, int nslot
   }
 }
 
-static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long long p, const float *dy,
-                           long long dy_bstride, const float *x, long long x_bstride,
-                           const float *x_coef, int x_relu, float *dw, void *workspace,
-                           size_t workspace_bytes, const float *bnz, const float *bnb, float *dz,
-                           float *d_rb, int rb_group, hipStream_t s, bool defer = false,
-                           const float *k4_w = nullptr, const float *fdg_w = nullptr, float *fdg_part = nullptr,
-                           float *fdg_gpart = nullptr, const float *sp_ent = nullptr, int sp_ns = 0) {
-  NESIE_REQUIRE(nb >= 0 && ng >= 1 && co >= 1 && ci >= 1 && p >= 0 && dw, W);
+// One weight-gradient launch by name.  An entry point value-initialises it and fills the fields it
+// uses; the fused norm backward (pw_wgrad_bn_backward_impl) reads its own block, fills bnb and calls on.
+struct PwWgrad {
+  int nb, ng, co, ci; long long p;
+  const float *dy; long long dy_bs;             // dY (fused norm backward: dA; dy_bs is also Z's stride)
+  const float *x; long long x_bs;
+  const float *x_coef; int x_relu;
+  float *dw; void *workspace; size_t workspace_bytes;
+  int defer;                                    // != 0: the reduction stays pending (see "deferred reductions")
+  const float *bnz, *bnb; float *dz;            // BNB: Z, the finished coefficients [ng * co][8], dZ (may be dy)
+  float *d_rb; int rb_group;                    // ... the gradient of a row bias
+  const float *k4_w;                            // K4: x is X4 (nb, 4, p) and the 64 operand rows are rebuilt from it
+  const float *fdg_w; float *fdg_part, *fdg_gpart;   // FDG: the layer's weight, the input gradient's reductions
+  const float *sp_ent; int sp_ns;               // dY as a max-pool's entries (pw_wgrad_sparse_kernel)
+  // read by pw_wgrad_bn_backward_impl only: what pw_bnb_coef_kernel turns into bnb (= coef_ws)
+  const float *z_coef, *gamma, *part; int nslots;
+  float *dgamma, *dbeta, *coef_ws;
+};
+
+// dynamic LDS of a pw_wgrad_kernel launch: two tiles (FDG: each with the four X4 rows behind it)
+constexpr size_t pw_wgrad_lds(int co16, int ci16, bool fdg = false) {
+  return (size_t)2 * ((co16 + ci16) * 16 * 36 + (fdg ? 4 * 36 : 0)) * sizeof(float);
+}
+
+// Launch a 512-thread kernel whose dynamic LDS exceeds the default limit: the limit is raised at the
+// first launch of each kernel instantiation (the flag belongs to this template's instantiation).
+template <auto Kern, typename... Args>
+static void launch_lds(dim3 grid, size_t lds, hipStream_t s, Args... args) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = true;
+  }
+  hipLaunchKernelGGL(Kern, grid, dim3(512), lds, s, args...);
+}
+
+// leave a launch's reduction to nesie_pw_wgrad_flush_deferred (a full table is flushed first)
+static int rd_defer(const RDesc &d, hipStream_t s) {
+  if (g_pending.n == RD_MAX) { const int st = rd_flush(s); if (st) return st; }
+  rd_push(d);
+  return NESIE_OK;
+}
+
+static int pw_wgrad_launch(const char *W, const PwWgrad &d, hipStream_t s) {
+  const int nb = d.nb, ng = d.ng, co = d.co, ci = d.ci;
+  const long long p = d.p;
+  NESIE_REQUIRE(nb >= 0 && ng >= 1 && co >= 1 && ci >= 1 && p >= 0 && d.dw, W);
   // (sp_ent: dY is given as a max-pool's entries and the partials come from pw_wgrad_sparse_kernel)
-  NESIE_REQUIRE(!sp_ent || (co == 128 && ci == 256 && (sp_ns == 16 || sp_ns == 64) && p % sp_ns == 0 && x_coef && x_relu &&
-                            !bnb && !d_rb && !k4_w && ((uintptr_t)sp_ent & 7) == 0), W);
-  auto launch_sparse = [&](float *partial, int nwg, int rev, int tiled) {
-    const size_t lds = (size_t)2 * 256 * 36 * sizeof(float) + 256 * sizeof(float2);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void *)pw_wgrad_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = true;
-    }
-    hipLaunchKernelGGL(pw_wgrad_sparse_kernel, dim3(nwg * ng), dim3(512), lds, s, nb, ng, p, x, x_bstride, x_coef,
-                       (const float2 *)sp_ent, sp_ns == 16 ? 4 : 6, (int)(p / sp_ns), partial, nwg, rev, tiled);
-  };
+  NESIE_REQUIRE(!d.sp_ent || (co == 128 && ci == 256 && (d.sp_ns == 16 || d.sp_ns == 64) && p % d.sp_ns == 0 && d.x_coef &&
+                              d.x_relu && !d.bnb && !d.d_rb && !d.k4_w && ((uintptr_t)d.sp_ent & 7) == 0), W);
   // (k4_w: x is X4 (nb, 4, p) and the 64 operand rows are rebuilt from it -- one build)
-  NESIE_REQUIRE(!k4_w || (co == 64 && ci == 64 && ng == 1 && bnb && x_coef && !d_rb && x_bstride >= 4 * p &&
-                          ((uintptr_t)k4_w & 15) == 0), W);
+  NESIE_REQUIRE(!d.k4_w || (co == 64 && ci == 64 && ng == 1 && d.bnb && d.x_coef && !d.d_rb && d.x_bs >= 4 * p &&
+                            ((uintptr_t)d.k4_w & 15) == 0), W);
   if (nb == 0 || p == 0) {
-    (void)hipMemsetAsync(dw, 0, (size_t)ng * co * ci * sizeof(float), s);
+    (void)hipMemsetAsync(d.dw, 0, (size_t)ng * co * ci * sizeof(float), s);
     return NESIE_OK;
   }
-  const bool tiled_mode = !bnb && !d_rb && pw_wgrad_tiled(nb, ng, co, ci, p);
+  const bool tiled_mode = !d.bnb && !d.d_rb && pw_wgrad_tiled(nb, ng, co, ci, p);
   if (!tiled_mode && !nesie_pw_wgrad_supported(co, ci, p)) {
     set_error("%s: %d x %d over %lld positions is outside the built tiles", W, co, ci, p);
     return NESIE_ERR_UNSUPPORTED;
   }
-  NESIE_REQUIRE(nb % ng == 0 && (dy || sp_ent) && x && workspace, W);
-  NESIE_REQUIRE(workspace_bytes >= nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p), W);
-  NESIE_REQUIRE((((uintptr_t)dy | (uintptr_t)x) & 15) == 0 && (dy_bstride & 3) == 0 && (x_bstride & 3) == 0, W);
+  NESIE_REQUIRE(nb % ng == 0 && (d.dy || d.sp_ent) && d.x && d.workspace, W);
+  NESIE_REQUIRE(d.workspace_bytes >= nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p), W);
+  NESIE_REQUIRE((((uintptr_t)d.dy | (uintptr_t)d.x) & 15) == 0 && (d.dy_bs & 3) == 0 && (d.x_bs & 3) == 0, W);
   NESIE_REQUIRE((long long)(co > ci ? co : ci) * p < (1ll << 30), W);
   NESIE_REQUIRE((long long)(nb / ng) * (p / 32) < (1ll << 30), W);     // (32-bit tile cursor)
-  const float lo0 = x_relu ? 0.f : -__builtin_inff();
+  const float lo = d.x_relu ? 0.f : -__builtin_inff();
   // dY is the tensor a launch has just written: a big one is read last tile first (nesie_lib.hip)
   const int rev = walk_dir((long long)nb * co * p * 4);
+  float *partial = (float *)d.workspace;
+  // one launch: the columns [xc, xc + cw) of the product on `grid`, with nwg workgroups per weight group
+  int nwg = 0, cw = 0;
+  dim3 grid;
+  const float *xc = nullptr, *cc = nullptr;
+  auto launch_sparse = [&](int tiled) {
+    launch_lds<pw_wgrad_sparse_kernel>(dim3(nwg * ng), (size_t)2 * 256 * 36 * sizeof(float) + 256 * sizeof(float2), s, nb,
+                                       ng, p, d.x, d.x_bs, d.x_coef, (const float2 *)d.sp_ent, d.sp_ns == 16 ? 4 : 6,
+                                       (int)(p / d.sp_ns), partial, nwg, rev, tiled);
+  };
+#define LKL(LDS, ...)                                                                                                  \
+  launch_lds<pw_wgrad_kernel<__VA_ARGS__>>(grid, LDS, s, nb, ng, co, cw, p, d.dy, d.dy_bs, xc, d.x_bs, cc, ci, lo,     \
+                                           partial, nwg, d.bnz, d.bnb, d.dz, d.d_rb, d.rb_group, rev, d.k4_w, d.fdg_w, \
+                                           d.fdg_part, d.fdg_gpart)
+#define LK(CO16, CI16, ...) LKL(pw_wgrad_lds(CO16, CI16), CO16, CI16, __VA_ARGS__)
   if (tiled_mode) {
-    const int nwg = pw_wgrad_tiled_nwg(nb, ng, co, ci, p);
+    nwg = pw_wgrad_tiled_nwg(nb, ng, co, ci, p);
     const int nrb = cdiv(co, TILED_B), ncb = cdiv(ci, TILED_B);
-    float *partial = (float *)workspace;
-    const size_t lds = (size_t)2 * (4 + 4) * 16 * 36 * sizeof(float);
-#define LT(AFF)                                                                                        \
-    do {                                                                                               \
-      auto kern = pw_wgrad_kernel<4, 4, 2, 4, AFF, false>;                                             \
-      static bool attr = false;                                                                        \
-      if (!attr) {                                                                                     \
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        attr = true;                                                                                   \
-      }                                                                                                \
-      hipLaunchKernelGGL(kern, dim3(nwg * ng, nrb, ncb), dim3(512), lds, s, nb, ng, co, ci, p, dy, dy_bstride, x, \
-                         x_bstride, x_coef, ci, lo0, partial, nwg, (const float *)nullptr, (const float *)nullptr, \
-                         (float *)nullptr, (float *)nullptr, 0, rev, (const float *)nullptr,            \
-                         (const float *)nullptr, (float *)nullptr, (float *)nullptr);                   \
-    } while (0)
-    if (sp_ent) launch_sparse(partial, nwg, rev, 1);
-    else if (x_coef) LT(true); else LT(false);
-#undef LT
-    if (defer) {
-      if (g_pending.n == RD_MAX) { const int st = rd_flush(s); if (st) return st; }
-      RDesc d{};
-      d.part = partial; d.dw = dw; d.kind = 1; d.nparts = nwg; d.ci = ci; d.co = co; d.ng = ng;
-      d.br = TILED_B; d.bc = TILED_B; d.nblk = nrb * ncb;
-      rd_push(d);
-      return check_launch(W);
+    grid = dim3(nwg * ng, nrb, ncb);
+    cw = ci; xc = d.x; cc = d.x_coef;
+    if (d.sp_ent) launch_sparse(1);
+    else if (d.x_coef) LK(4, 4, 2, 4, true, false); else LK(4, 4, 2, 4, false, false);
+    if (d.defer) {
+      RDesc r{};
+      r.part = partial; r.dw = d.dw; r.kind = 1; r.nparts = nwg; r.ci = ci; r.co = co; r.ng = ng;
+      r.br = TILED_B; r.bc = TILED_B; r.nblk = nrb * ncb;
+      const int st = rd_defer(r, s);
+      return st ? st : check_launch(W);
     }
     hipLaunchKernelGGL(pw_wgrad_reduce_tiled_kernel, dim3(cdiv(TILED_B * TILED_B, 256), nrb * ncb, ng), dim3(256), 0, s,
-                       co, ci, TILED_B, TILED_B, nwg, partial, dw);
+                       co, ci, TILED_B, TILED_B, nwg, partial, d.dw);
     return check_launch(W);
   }
   const int block = pw_wgrad_block(co, ci);
   // (the fused norm backward writes dZ while it forms it: one launch must own every column)
-  NESIE_REQUIRE(!bnb || (bnz && dz && block == ci && (((uintptr_t)bnz | (uintptr_t)dz) & 15) == 0), W);
-  NESIE_REQUIRE(!d_rb || (bnb && (rb_group == 16 || rb_group == 64) && p % rb_group == 0 &&
-                          dy_bstride == (long long)co * p), W);
-  const int nwg = pw_wgrad_nwg(nb, ng, p, co, block, bnb != nullptr);
-  float *partial = (float *)workspace;
-  const float lo = x_relu ? 0.f : -__builtin_inff();
-#define LK(CO16, CI16, WM, WN, AFF, BNB)                                                         \
-  do {                                                                                           \
-    const size_t lds = (size_t)2 * (CO16 + CI16) * 16 * 36 * sizeof(float);                      \
-    auto kern = pw_wgrad_kernel<CO16, CI16, WM, WN, AFF, BNB>;                                   \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL(kern, dim3(nwg * ng), dim3(512), lds, s, nb, ng, co, cw, p, dy,           \
-                       dy_bstride, xc, x_bstride, cc, ci, lo, partial, nwg, bnz, bnb, dz, d_rb, rb_group, rev, \
-                       (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr); \
-  } while (0)
-#define L(CO16, CI16, WM, WN)                                                                    \
-  do {                                                                                           \
-    if (bnb) { if (x_coef) LK(CO16, CI16, WM, WN, true, true); else LK(CO16, CI16, WM, WN, false, true); } \
-    else { if (x_coef) LK(CO16, CI16, WM, WN, true, false); else LK(CO16, CI16, WM, WN, false, false); }   \
+  NESIE_REQUIRE(!d.bnb || (d.bnz && d.dz && block == ci && (((uintptr_t)d.bnz | (uintptr_t)d.dz) & 15) == 0), W);
+  NESIE_REQUIRE(!d.d_rb || (d.bnb && (d.rb_group == 16 || d.rb_group == 64) && p % d.rb_group == 0 &&
+                            d.dy_bs == (long long)co * p), W);
+  nwg = pw_wgrad_nwg(nb, ng, p, co, block, d.bnb != nullptr);
+  grid = dim3(nwg * ng);
+#define L(CO16, CI16, WM, WN)                                                                                          \
+  do {                                                                                                                 \
+    if (d.bnb) { if (d.x_coef) LK(CO16, CI16, WM, WN, true, true); else LK(CO16, CI16, WM, WN, false, true); }         \
+    else { if (d.x_coef) LK(CO16, CI16, WM, WN, true, false); else LK(CO16, CI16, WM, WN, false, false); }             \
   } while (0)
   for (int c0 = 0; c0 < ci; c0 += block) {     // column blocks [c0, c0 + cw) of dw; same stream: the
-    const int cw = ci - c0 < block ? ci - c0 : block;   // workspace is free again when the next one starts
-    const float *xc = x + (size_t)c0 * p;
-    const float *cc = x_coef ? x_coef + (size_t)c0 * 4 : nullptr;
-    if (k4_w && fdg_w) {     // ... with the input gradient's reductions in the same launch (dz is not written)
-      NESIE_REQUIRE(fdg_part && fdg_gpart && ((uintptr_t)fdg_gpart & 15) == 0 && ((uintptr_t)fdg_part & 7) == 0, W);
-      const size_t lds = (size_t)2 * ((4 + 4) * 16 * 36 + 4 * 36) * sizeof(float);
-      auto kern = pw_wgrad_kernel<4, 4, 2, 4, true, true, true, true>;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(nwg * ng), dim3(512), lds, s, nb, ng, co, cw, p, dy, dy_bstride, xc, x_bstride, cc,
-                         ci, lo, partial, nwg, bnz, bnb, dz, d_rb, rb_group, rev, k4_w, fdg_w, fdg_part, fdg_gpart);
-    } else if (k4_w) {
-      const size_t lds = (size_t)2 * (4 + 4) * 16 * 36 * sizeof(float);
-      auto kern = pw_wgrad_kernel<4, 4, 2, 4, true, true, true>;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(nwg * ng), dim3(512), lds, s, nb, ng, co, cw, p, dy, dy_bstride, xc, x_bstride, cc,
-                         ci, lo, partial, nwg, bnz, bnb, dz, d_rb, rb_group, rev, k4_w, (const float *)nullptr,
-                         (float *)nullptr, (float *)nullptr);
-    } else if (sp_ent) launch_sparse(partial, nwg, rev, 0);      // (block == ci: one pass of this loop)
+    cw = ci - c0 < block ? ci - c0 : block;    // workspace is free again when the next one starts
+    xc = d.x + (size_t)c0 * p;
+    cc = d.x_coef ? d.x_coef + (size_t)c0 * 4 : nullptr;
+    if (d.k4_w && d.fdg_w) { // ... with the input gradient's reductions in the same launch (dz is not written)
+      NESIE_REQUIRE(d.fdg_part && d.fdg_gpart && ((uintptr_t)d.fdg_gpart & 15) == 0 && ((uintptr_t)d.fdg_part & 7) == 0, W);
+      LKL(pw_wgrad_lds(4, 4, true), 4, 4, 2, 4, true, true, true, true);
+    } else if (d.k4_w) LK(4, 4, 2, 4, true, true, true);
+    else if (d.sp_ent) launch_sparse(0);      // (block == ci: one pass of this loop)
     else if (co <= 64 && cw <= 64) L(4, 4, 2, 4);
     else if (co <= 128 && cw <= 64) L(8, 4, 4, 2);
     else if (co <= 128 && cw <= 128) L(8, 8, 2, 4);
@@ -841,42 +838,48 @@ static int pw_wgrad_launch(const char *W, int nb, int ng, int co, int ci, long l
     else if (co <= 128) L(8, 20, 2, 4);
     else L(16, 8, 4, 2);
     const int total = co * cw;
-    if (defer && block >= ci) {      // (column blocks share the workspace: only a whole-product launch may wait)
-      if (g_pending.n == RD_MAX) { const int st = rd_flush(s); if (st) return st; }
-      RDesc d{};
-      d.part = partial; d.dw = dw; d.kind = 0; d.nparts = nwg; d.total = total; d.ci = cw; d.ld = ci; d.col0 = c0;
-      d.co = co; d.ng = ng;
-      rd_push(d);
+    if (d.defer && block >= ci) {    // (column blocks share the workspace: only a whole-product launch may wait)
+      RDesc r{};
+      r.part = partial; r.dw = d.dw; r.kind = 0; r.nparts = nwg; r.total = total; r.ci = cw; r.ld = ci; r.col0 = c0;
+      r.co = co; r.ng = ng;
+      const int st = rd_defer(r, s);
+      if (st) return st;
       continue;
     }
     hipLaunchKernelGGL(pw_wgrad_reduce_kernel, dim3(cdiv(total, 64), ng), dim3(1024), 0, s, total, nwg,
-                       partial, dw, cw, ci, c0, co);
+                       partial, d.dw, cw, ci, c0, co);
   }
 #undef L
 #undef LK
+#undef LKL
   return check_launch(W);
+}
+
+// the fields every entry point sets: the problem, the destination and its scratch
+static PwWgrad pw_wgrad_problem(int nb, int ng, int co, int ci, long long p, float *dw, void *workspace,
+                                size_t workspace_bytes) {
+  PwWgrad d{};
+  d.nb = nb; d.ng = ng; d.co = co; d.ci = ci; d.p = p;
+  d.dw = dw; d.workspace = workspace; d.workspace_bytes = workspace_bytes;
+  return d;
 }
 }  // namespace nesie
 
+// defer != 0 (here and in every weight-gradient entry point below): the launch leaves its reduction
+// pending (see "deferred reductions"): dw is written by nesie_pw_wgrad_flush_deferred; `workspace`
+// must stay untouched until then.
 extern "C" int nesie_pw_wgrad(int nb, int ng, int co, int ci, long long p, const float *dy,
                               long long dy_bstride, const float *x, long long x_bstride,
                               const float *x_coef, int x_relu, float *dw, void *workspace,
-                              size_t workspace_bytes, void *stream) {
-  return pw_wgrad_launch("pw_wgrad", nb, ng, co, ci, p, dy, dy_bstride, x, x_bstride, x_coef, x_relu, dw,
-                         workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+                              size_t workspace_bytes, int defer, void *stream) {
+  PwWgrad d = pw_wgrad_problem(nb, ng, co, ci, p, dw, workspace, workspace_bytes);
+  d.dy = dy; d.dy_bs = dy_bstride;
+  d.x = x; d.x_bs = x_bstride; d.x_coef = x_coef; d.x_relu = x_relu;
+  d.defer = defer;
+  return pw_wgrad_launch("pw_wgrad", d, (hipStream_t)stream);
 }
 
-// The same launch with its reduction left pending (see "deferred reductions"): dw is written by
-// nesie_pw_wgrad_flush_deferred; `workspace` must stay untouched until then.
-extern "C" int nesie_pw_wgrad_deferred(int nb, int ng, int co, int ci, long long p, const float *dy,
-                                       long long dy_bstride, const float *x, long long x_bstride,
-                                       const float *x_coef, int x_relu, float *dw, void *workspace,
-                                       size_t workspace_bytes, void *stream) {
-  return pw_wgrad_launch("pw_wgrad_deferred", nb, ng, co, ci, p, dy, dy_bstride, x, x_bstride, x_coef, x_relu, dw,
-                         workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, true);
-}
-
-// nesie_pw_wgrad / _deferred for a dY that is a max-pool's gradient given as entries (pw_wgrad_sparse_kernel):
+// nesie_pw_wgrad for a dY that is a max-pool's gradient given as entries (pw_wgrad_sparse_kernel):
 // dw and every partial bit for bit what the dense launch over the expanded tensor leaves
 extern "C" int nesie_pw_wgrad_sparse_supported(int co, int ci, long long p, int ns) {
   return co == 128 && ci == 256 && (ns == 16 || ns == 64) && p >= ns && p % ns == 0 && p % 32 == 0 &&
@@ -884,21 +887,14 @@ extern "C" int nesie_pw_wgrad_sparse_supported(int co, int ci, long long p, int 
 }
 extern "C" int nesie_pw_wgrad_sparse(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
                                      const float *x, long long x_bstride, const float *x_coef, float *dw,
-                                     void *workspace, size_t workspace_bytes, void *stream) {
+                                     void *workspace, size_t workspace_bytes, int defer, void *stream) {
   const char *W = "pw_wgrad_sparse";
   NESIE_REQUIRE(ent && nesie_pw_wgrad_sparse_supported(co, ci, p, ns), W);
-  return pw_wgrad_launch(W, nb, ng, co, ci, p, nullptr, 0, x, x_bstride, x_coef, 1, dw, workspace, workspace_bytes,
-                         nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, false, nullptr, nullptr, nullptr,
-                         nullptr, ent, ns);
-}
-extern "C" int nesie_pw_wgrad_sparse_deferred(int nb, int ng, int co, int ci, long long p, int ns, const float *ent,
-                                              const float *x, long long x_bstride, const float *x_coef, float *dw,
-                                              void *workspace, size_t workspace_bytes, void *stream) {
-  const char *W = "pw_wgrad_sparse_deferred";
-  NESIE_REQUIRE(ent && nesie_pw_wgrad_sparse_supported(co, ci, p, ns), W);
-  return pw_wgrad_launch(W, nb, ng, co, ci, p, nullptr, 0, x, x_bstride, x_coef, 1, dw, workspace, workspace_bytes,
-                         nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, true, nullptr, nullptr, nullptr,
-                         nullptr, ent, ns);
+  PwWgrad d = pw_wgrad_problem(nb, ng, co, ci, p, dw, workspace, workspace_bytes);
+  d.x = x; d.x_bs = x_bstride; d.x_coef = x_coef; d.x_relu = 1;
+  d.sp_ent = ent; d.sp_ns = ns;
+  d.defer = defer;
+  return pw_wgrad_launch(W, d, (hipStream_t)stream);
 }
 
 extern "C" int nesie_pw_wgrad_flush_deferred(void *stream) { return rd_flush((hipStream_t)stream); }
@@ -912,28 +908,22 @@ extern "C" int nesie_pw_wgrad_bn_supported(int co, int ci, long long p) {
   return nesie_pw_wgrad_supported(co, ci, p) && pw_wgrad_block(co, ci) == ci ? 1 : 0;
 }
 
-static int pw_wgrad_bn_backward_impl(const char *W, bool defer, int nb, int ng, int co, int ci, long long p, const float *da,
-                                          const float *z, long long z_bstride, const float *z_coef,
-                                          const float *gamma, const float *part, int nslots,
-                                          const float *x, long long x_bstride, const float *x_coef,
-                                          int x_relu, float *dz, float *dw, float *dgamma, float *dbeta,
-                                          float *coef_ws, float *d_row_bias, int rb_group,
-                                          void *workspace, size_t workspace_bytes, void *stream,
-                                          const float *k4_w = nullptr, const float *fdg_w = nullptr,
-                                          float *fdg_part = nullptr, float *fdg_gpart = nullptr) {
-  NESIE_REQUIRE(nb >= 0 && ng >= 1 && co >= 1 && nslots >= 1, W);
+// The fused norm backward: d.dy = dA, d.bnz = Z (both at d.dy_bs), d.dz and the block pw_bnb_coef_kernel
+// reads are filled by the entry point; the coefficients it leaves in coef_ws are the launch's bnb.
+static int pw_wgrad_bn_backward_impl(const char *W, PwWgrad d, void *stream) {
+  const int nb = d.nb, ng = d.ng, co = d.co;
+  NESIE_REQUIRE(nb >= 0 && ng >= 1 && co >= 1 && d.nslots >= 1, W);
   hipStream_t s = (hipStream_t)stream;
-  if (nb == 0 || p == 0) {
-    if (dgamma) (void)hipMemsetAsync(dgamma, 0, (size_t)ng * co * sizeof(float), s);
-    if (dbeta) (void)hipMemsetAsync(dbeta, 0, (size_t)ng * co * sizeof(float), s);
-    return pw_wgrad_launch(W, nb, ng, co, ci, p, da, z_bstride, x, x_bstride, x_coef, x_relu, dw, workspace,
-                           workspace_bytes, nullptr, nullptr, nullptr, nullptr, 0, s, defer);
+  if (nb == 0 || d.p == 0) {     // (dw is zero-filled; nothing of the fused block is read)
+    if (d.dgamma) (void)hipMemsetAsync(d.dgamma, 0, (size_t)ng * co * sizeof(float), s);
+    if (d.dbeta) (void)hipMemsetAsync(d.dbeta, 0, (size_t)ng * co * sizeof(float), s);
+    return pw_wgrad_launch(W, d, s);
   }
-  NESIE_REQUIRE(da && z && z_coef && part && dz && coef_ws && nb % ng == 0, W);
-  hipLaunchKernelGGL(pw_bnb_coef_kernel, dim3(ng * co), dim3(64), 0, s, ng * co, nslots,
-                     (double)(nb / ng) * (double)p, part, z_coef, gamma, coef_ws, dgamma, dbeta);
-  return pw_wgrad_launch(W, nb, ng, co, ci, p, da, z_bstride, x, x_bstride, x_coef, x_relu, dw, workspace,
-                         workspace_bytes, z, coef_ws, dz, d_row_bias, rb_group, s, defer, k4_w, fdg_w, fdg_part, fdg_gpart);
+  NESIE_REQUIRE(d.dy && d.bnz && d.z_coef && d.part && d.dz && d.coef_ws && nb % ng == 0, W);
+  hipLaunchKernelGGL(pw_bnb_coef_kernel, dim3(ng * co), dim3(64), 0, s, ng * co, d.nslots,
+                     (double)(nb / ng) * (double)d.p, d.part, d.z_coef, d.gamma, d.coef_ws, d.dgamma, d.dbeta);
+  d.bnb = d.coef_ws;
+  return pw_wgrad_launch(W, d, s);
 }
 
 extern "C" int nesie_pw_wgrad_bn_backward(int nb, int ng, int co, int ci, long long p, const float *da,
@@ -942,28 +932,19 @@ extern "C" int nesie_pw_wgrad_bn_backward(int nb, int ng, int co, int ci, long l
                                           const float *x, long long x_bstride, const float *x_coef,
                                           int x_relu, float *dz, float *dw, float *dgamma, float *dbeta,
                                           float *coef_ws, float *d_row_bias, int rb_group,
-                                          void *workspace, size_t workspace_bytes, void *stream) {
-  return pw_wgrad_bn_backward_impl("pw_wgrad_bn_backward", false, nb, ng, co, ci, p, da, z, z_bstride, z_coef, gamma,
-                                   part, nslots, x, x_bstride, x_coef, x_relu, dz, dw, dgamma, dbeta, coef_ws,
-                                   d_row_bias, rb_group, workspace, workspace_bytes, stream);
+                                          void *workspace, size_t workspace_bytes, int defer, void *stream) {
+  PwWgrad d = pw_wgrad_problem(nb, ng, co, ci, p, dw, workspace, workspace_bytes);
+  d.dy = da; d.bnz = z; d.dy_bs = z_bstride; d.dz = dz;
+  d.z_coef = z_coef; d.gamma = gamma; d.part = part; d.nslots = nslots;
+  d.x = x; d.x_bs = x_bstride; d.x_coef = x_coef; d.x_relu = x_relu;
+  d.dgamma = dgamma; d.dbeta = dbeta; d.coef_ws = coef_ws;
+  d.d_rb = d_row_bias; d.rb_group = rb_group;
+  d.defer = defer;
+  return pw_wgrad_bn_backward_impl("pw_wgrad_bn_backward", d, stream);
 }
-
-// ... and with the weight gradient's reduction left pending (dz, dgamma, dbeta are complete on return)
-extern "C" int nesie_pw_wgrad_bn_backward_deferred(int nb, int ng, int co, int ci, long long p, const float *da,
-                                                   const float *z, long long z_bstride, const float *z_coef,
-                                                   const float *gamma, const float *part, int nslots,
-                                                   const float *x, long long x_bstride, const float *x_coef,
-                                                   int x_relu, float *dz, float *dw, float *dgamma, float *dbeta,
-                                                   float *coef_ws, float *d_row_bias, int rb_group,
-                                                   void *workspace, size_t workspace_bytes, void *stream) {
-  return pw_wgrad_bn_backward_impl("pw_wgrad_bn_backward_deferred", true, nb, ng, co, ci, p, da, z, z_bstride, z_coef,
-                                   gamma, part, nslots, x, x_bstride, x_coef, x_relu, dz, dw, dgamma, dbeta, coef_ws,
-                                   d_row_bias, rb_group, workspace, workspace_bytes, stream);
-}
-
 
 // ... of SA1's second layer (64 x 64), whose X is the REBUILT output of the first: x4 (nb, 4, p),
-// w0 (64, 4), x_coef the first layer's folded norm.  defer != 0: the reduction stays pending.
+// w0 (64, 4), x_coef the first layer's folded norm.
 extern "C" int nesie_pw_wgrad_bn_backward_k4(int nb, long long p, const float *da, const float *z,
                                              long long z_bstride, const float *z_coef, const float *gamma,
                                              const float *part, int nslots, const float *x4,
@@ -972,9 +953,13 @@ extern "C" int nesie_pw_wgrad_bn_backward_k4(int nb, long long p, const float *d
                                              void *workspace, size_t workspace_bytes, int defer, void *stream) {
   const char *W = "pw_wgrad_bn_backward_k4";
   NESIE_REQUIRE(nb >= 1 && p >= 32 && x4 && w0 && x_coef, W);
-  return pw_wgrad_bn_backward_impl(W, defer != 0, nb, 1, 64, 64, p, da, z, z_bstride, z_coef, gamma, part, nslots, x4,
-                                   x4_bstride, x_coef, 1, dz, dw, dgamma, dbeta, coef_ws, nullptr, 0, workspace,
-                                   workspace_bytes, stream, w0);
+  PwWgrad d = pw_wgrad_problem(nb, 1, 64, 64, p, dw, workspace, workspace_bytes);
+  d.dy = da; d.bnz = z; d.dy_bs = z_bstride; d.dz = dz;
+  d.z_coef = z_coef; d.gamma = gamma; d.part = part; d.nslots = nslots;
+  d.x = x4; d.x_bs = x4_bstride; d.x_coef = x_coef; d.x_relu = 1; d.k4_w = w0;
+  d.dgamma = dgamma; d.dbeta = dbeta; d.coef_ws = coef_ws;
+  d.defer = defer;
+  return pw_wgrad_bn_backward_impl(W, d, stream);
 }
 
 // ... and with the reductions of the layer's INPUT gradient from the same launch (pw_wgrad_kernel,
@@ -994,9 +979,14 @@ extern "C" int nesie_pw_wgrad_bn_backward_k4_fused(int nb, long long p, const fl
                                                    void *stream) {
   const char *W = "pw_wgrad_bn_backward_k4_fused";
   NESIE_REQUIRE(nb >= 1 && p >= 32 && x4 && w0 && x_coef && w && in_part && in_gpart, W);
-  return pw_wgrad_bn_backward_impl(W, defer != 0, nb, 1, 64, 64, p, da, z, z_bstride, z_coef, gamma, part, nslots, x4,
-                                   x4_bstride, x_coef, 1, const_cast<float *>(da), dw, dgamma, dbeta, coef_ws, nullptr, 0,
-                                   workspace, workspace_bytes, stream, w0, w, in_part, in_gpart);
+  PwWgrad d = pw_wgrad_problem(nb, 1, 64, 64, p, dw, workspace, workspace_bytes);
+  d.dy = da; d.bnz = z; d.dy_bs = z_bstride; d.dz = const_cast<float *>(da);
+  d.z_coef = z_coef; d.gamma = gamma; d.part = part; d.nslots = nslots;
+  d.x = x4; d.x_bs = x4_bstride; d.x_coef = x_coef; d.x_relu = 1; d.k4_w = w0;
+  d.fdg_w = w; d.fdg_part = in_part; d.fdg_gpart = in_gpart;
+  d.dgamma = dgamma; d.dbeta = dbeta; d.coef_ws = coef_ws;
+  d.defer = defer;
+  return pw_wgrad_bn_backward_impl(W, d, stream);
 }
 
 // The reduction coefficients of a BatchNorm + ReLU backward on their own (for a consumer of dZ

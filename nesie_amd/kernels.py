@@ -705,7 +705,7 @@ class HipKernels:
         (wide layers over few positions: the 1-D chains)."""
         return bool(_lib.load().nesie_pw_wgrad_tiled(int(nb), int(ng), int(co), int(ci), int(p)))
 
-    # ---- deferred weight-gradient reductions (nesie_pw_wgrad_deferred, include/nesie_ops.h) -----
+    # ---- deferred weight-gradient reductions ("Deferred reductions", include/nesie_ops.h) -------
     # Between ``begin_deferred_reductions()`` and ``flush_deferred_reductions()`` a weight gradient
     # whose destination is FINAL (a slot of the flat gradient vector: nothing reads it before the
     # optimiser) leaves the addition of its partials pending; the flush runs them all in one launch.
@@ -736,6 +736,19 @@ class HipKernels:
             cls._deferred = None
         return done
 
+    @staticmethod
+    def _wgrad_scratch(nb, ng, co, ci, p, dw, final):
+        """Scratch of one weight-gradient launch into ``dw`` -> (workspace, its bytes, defer).
+        defer: ``final`` and a window is open; (workspace, dw) is then held BEFORE the launch, so that
+        a launch that raises after the library queued its reduction still leaves a non-empty list and
+        the next ``begin_deferred_reductions()`` drops the queue (which points at this workspace)."""
+        need = _lib.load().nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
+        ws = _workspace(need, dw.device)
+        defer = bool(final) and HipKernels._deferred is not None
+        if defer:
+            HipKernels._deferred.append((ws, dw))
+        return ws, need, defer
+
     def pw_wgrad(self, dy, x, dw, ng=1, x_coef=None, x_relu=True, final=False):
         """dw (ng, co, ci) = sum over n % ng == g and positions of dy[n] (co, P) act(x[n])^T
         (nesie_pw_wgrad); dy (NB, co, P), x (NB, ci, P) batch-strided views allowed;
@@ -750,15 +763,9 @@ class HipKernels:
         if x_coef is not None:
             _check(x_coef); _f32(x_coef)
             assert tuple(x_coef.shape) == (ng * ci, 4)
-        lib = _lib.load()
-        need = lib.nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
-        defer = final and HipKernels._deferred is not None
-        ws = _workspace(need, dy.device)
-        _launch("nesie_pw_wgrad_deferred" if defer else "nesie_pw_wgrad", dy, nb, ng, co, ci, p, dy,
-                dy.stride(0) if nb > 1 else co * p, x, x.stride(0) if nb > 1 else ci * p, x_coef,
-                bool(x_relu), dw, ws, need)
-        if defer:
-            HipKernels._deferred.append((ws, dw))
+        ws, need, defer = self._wgrad_scratch(nb, ng, co, ci, p, dw, final)
+        _launch("nesie_pw_wgrad", dy, nb, ng, co, ci, p, dy, dy.stride(0) if nb > 1 else co * p, x,
+                x.stride(0) if nb > 1 else ci * p, x_coef, bool(x_relu), dw, ws, need, defer)
 
     def pw_bnb_coef(self, part, z_coef, gamma, count, dgamma, dbeta):
         """(channels, 8) reduction coefficients of a BatchNorm + ReLU backward from the partial sums
@@ -802,17 +809,11 @@ class HipKernels:
         if x_coef is not None:
             _check(x_coef); _f32(x_coef)
             assert tuple(x_coef.shape) == (ng * ci, 4)
-        lib = _lib.load()
-        need = lib.nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
-        defer = final and HipKernels._deferred is not None
-        ws = _workspace(need, da.device)
+        ws, need, defer = self._wgrad_scratch(nb, ng, co, ci, p, dw, final)
         cws = torch.empty(ng * co, 8, dtype=torch.float32, device=da.device)
-        if defer:
-            HipKernels._deferred.append((ws, dw))
-        _launch("nesie_pw_wgrad_bn_backward_deferred" if defer else "nesie_pw_wgrad_bn_backward",
-                da, nb, ng, co, ci, p, da, z, co * p, z_coef, gamma, part, part.shape[1], x,
-                x.stride(0) if nb > 1 else ci * p, x_coef, bool(x_relu), dz, dw, dgamma, dbeta, cws,
-                d_row_bias, int(group), ws, need)
+        _launch("nesie_pw_wgrad_bn_backward", da, nb, ng, co, ci, p, da, z, co * p, z_coef, gamma,
+                part, part.shape[1], x, x.stride(0) if nb > 1 else ci * p, x_coef, bool(x_relu), dz,
+                dw, dgamma, dbeta, cws, d_row_bias, int(group), ws, need, defer)
 
     @staticmethod
     def conv_wgrad_supported(cout, cin):
@@ -966,15 +967,11 @@ class HipKernels:
         assert tuple(z_coef.shape) == (64, 4) == tuple(x_coef.shape) and part.shape[0] == 64 and part.shape[2] == 2
         if gamma is not None:
             _check(gamma); _f32(gamma)
-        need = _lib.load().nesie_pw_wgrad_workspace_bytes(nb, 1, 64, 64, p)
-        defer = final and HipKernels._deferred is not None
-        ws = _workspace(need, da.device)
+        ws, need, defer = self._wgrad_scratch(nb, 1, 64, 64, p, dw, final)
         cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
-        if defer:
-            HipKernels._deferred.append((ws, dw))
         _launch("nesie_pw_wgrad_bn_backward_k4", da, nb, p, da, z, 64 * p, z_coef, gamma, part,
                 part.shape[1], x4, x4.stride(0) if nb > 1 else 4 * p, w0, x_coef, da, dw, dgamma,
-                dbeta, cws, ws, need, int(defer))
+                dbeta, cws, ws, need, defer)
 
     def pw_wgrad_bn_backward_k4_fused(self, da, z, z_coef, gamma, part, x4, w0, x_coef, w, dw, dgamma, dbeta,
                                       final=False):
@@ -987,19 +984,14 @@ class HipKernels:
         assert tuple(z_coef.shape) == (64, 4) == tuple(x_coef.shape) and part.shape[0] == 64 and part.shape[2] == 2
         if gamma is not None:
             _check(gamma); _f32(gamma)
-        lib = _lib.load()
-        need = lib.nesie_pw_wgrad_workspace_bytes(nb, 1, 64, 64, p)
-        slots = lib.nesie_pw_wgrad_bn_backward_k4_slots(nb, p)
-        defer = final and HipKernels._deferred is not None
-        ws = _workspace(need, da.device)
+        slots = _lib.load().nesie_pw_wgrad_bn_backward_k4_slots(nb, p)
+        ws, need, defer = self._wgrad_scratch(nb, 1, 64, 64, p, dw, final)
         cws = torch.empty(64, 8, dtype=torch.float32, device=da.device)
         in_part = torch.empty(64, slots, 2, dtype=torch.float32, device=da.device)
         in_gpart = torch.empty(64, slots, 4, dtype=torch.float32, device=da.device)
-        if defer:
-            HipKernels._deferred.append((ws, dw))
         _launch("nesie_pw_wgrad_bn_backward_k4_fused", da, nb, p, da, z, 64 * p, z_coef, gamma,
                 part, part.shape[1], x4, x4.stride(0) if nb > 1 else 4 * p, w0, x_coef, w, dw,
-                dgamma, dbeta, cws, in_part, in_gpart, ws, need, int(defer))
+                dgamma, dbeta, cws, in_part, in_gpart, ws, need, defer)
         return in_part, in_gpart
 
     def k4_moments(self, x4):
@@ -1267,11 +1259,8 @@ class HipKernels:
         if zstar is not None:
             _check(zstar); _f32(zstar)
             assert zstar.numel() == pooled.numel()
-            _launch("nesie_pw_pool_finish_z", pooled, nb, ng, c, p, group, pool_group, pmax, pmin,
-                    amax, amin, coef, bool(relu), pooled, argmax, zstar)
-            return
         _launch("nesie_pw_pool_finish", pooled, nb, ng, c, p, group, pool_group, pmax, pmin, amax,
-                amin, coef, bool(relu), pooled, argmax)
+                amin, coef, bool(relu), pooled, argmax, zstar)
 
     # ---- pooled tail without the dense pre-pool tensor (csrc/pool_tail.hip) ---------------------
     def pool_tail_supported(self, k, c, p, ns):
@@ -1359,13 +1348,9 @@ class HipKernels:
         assert tuple(ent.shape) == (nb, p // ns, co, 2) and p % ns == 0 and nb % ng == 0
         assert x.is_cuda and x.stride(2) == 1 and x.stride(1) == p
         assert dw.is_contiguous() and dw.numel() == ng * co * ci and tuple(x_coef.shape) == (ng * ci, 4)
-        need = _lib.load().nesie_pw_wgrad_workspace_bytes(nb, ng, co, ci, p)
-        defer = final and HipKernels._deferred is not None
-        ws = _workspace(need, x.device)
-        _launch("nesie_pw_wgrad_sparse_deferred" if defer else "nesie_pw_wgrad_sparse", x, nb, ng, co, ci, p,
-                int(ns), ent, x, x.stride(0) if nb > 1 else ci * p, x_coef, dw, ws, need)
-        if defer:
-            HipKernels._deferred.append((ws, dw))
+        ws, need, defer = self._wgrad_scratch(nb, ng, co, ci, p, dw, final)
+        _launch("nesie_pw_wgrad_sparse", x, nb, ng, co, ci, p, int(ns), ent, x,
+                x.stride(0) if nb > 1 else ci * p, x_coef, dw, ws, need, defer)
 
     def mlp_stat_finalize(self, part, count, gamma, beta, running_mean, running_var, momentum, eps,
                           coef, channel_major=False):

@@ -58,6 +58,16 @@ HAND_WRITTEN = {
     #  long long y_bstride, stat_part, int pool_group, pool_min, float *pool_max_out, pool_min_out,
     #  uint8_t *arg_max_out, arg_min_out, void *stream)
     "nesie_pw_layer_forward": (ctypes.c_int, "IIIIL" "PLPL" "II" "PIPIPP" "LP" "II" "PPPP" "P"),
+    # (int nb, ng, co, ci, long long p, dy, long long dy_bstride, x, long long x_bstride, x_coef,
+    #  int x_relu, float *dw, void *workspace, size_t workspace_bytes, int defer, void *stream)
+    "nesie_pw_wgrad": (ctypes.c_int, "IIIIL" "PLPL" "PIP" "PZ" "I" "P"),
+    # (int nb, ng, co, ci, long long p, da, z, long long z_bstride, z_coef, gamma, part, int nslots,
+    #  x, long long x_bstride, x_coef, int x_relu, float *dz, dw, dgamma, dbeta, coef_ws, d_row_bias,
+    #  int rb_group, void *workspace, size_t workspace_bytes, int defer, void *stream)
+    "nesie_pw_wgrad_bn_backward": (ctypes.c_int, "IIIIL" "PPL" "PPPI" "PLPI" "PPPPPP" "I" "PZ" "I" "P"),
+    # (int nb, ng, channels, long long p, int group, pool_group, pmax, pmin, const uint8_t *amax,
+    #  amin, coef, int relu, float *pooled, uint8_t *argmax, float *zstar, void *stream)
+    "nesie_pw_pool_finish": (ctypes.c_int, "IIILII" "PPPPP" "I" "PPP" "P"),
     # (int channels, nslots, double count, part, z_coef, gamma, bnb, dgamma, dbeta, stream)
     "nesie_pw_bnb_coef": (ctypes.c_int, "IID" "PPPPPP" "P"),
     # (int b, k, t, c, cls, bbox, surface, side, iou_s, iou, quality, int detach_sigma,
@@ -160,6 +170,27 @@ def test_invalid_arguments_return_a_status_not_a_crash():
     # empty problems succeed without touching the device
     assert lib.nesie_group_points_forward(0, 3, 5, 2, 2, None, None, None, None) == 0
     assert lib.nesie_furthest_point_sampling_wrapper(2, 10, 0, None, None, None, None) == 0
+
+
+def test_layer_entry_points_refuse_a_negative_batch_before_any_launch():
+    """The layer kernels' entry points with nb = -1: status 1, the message names the entry point, and
+    a call that asked for a deferred reduction has queued nothing.  The refusal comes before any HIP
+    call (safe without a GPU)."""
+    lib = _lib.load()
+    assert lib.nesie_abi_version() == 2
+    n = None
+    calls = {
+        "pw_layer_forward": lambda: lib.nesie_pw_layer_forward(
+            -1, 1, 64, 64, 64, n, 0, n, 0, 64, 1, n, 1, n, 0, n, n, 0, n, 0, 0, n, n, n, n, n),
+        "pw_wgrad": lambda: lib.nesie_pw_wgrad(-1, 1, 64, 64, 64, n, 0, n, 0, n, 1, n, n, 0, 1, n),
+        "pw_wgrad_bn_backward": lambda: lib.nesie_pw_wgrad_bn_backward(
+            -1, 1, 64, 64, 64, n, n, 0, n, n, n, 1, n, 0, n, 1, n, n, n, n, n, n, 0, n, 0, 1, n),
+        "pw_pool_finish": lambda: lib.nesie_pw_pool_finish(-1, 1, 64, 64, 16, 16, n, n, n, n, n, 1, n, n, n, n),
+    }
+    for name, call in calls.items():
+        assert call() == 1, name
+        assert name.encode() in lib.nesie_last_error(), name
+        assert lib.nesie_pw_wgrad_pending() == 0, name
 
 
 def test_product_path_refuses_cpu_tensors():

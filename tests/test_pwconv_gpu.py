@@ -980,10 +980,12 @@ def _lib_cu_count():
 
 
 def test_deferred_weight_gradient_reductions_equal_the_immediate_ones_bit_for_bit():
-    """nesie_pw_wgrad_deferred + nesie_pw_wgrad_flush_deferred: several weight gradients (whole-product
+    """nesie_pw_wgrad with defer + nesie_pw_wgrad_flush_deferred: several weight gradients (whole-product
     launches, a tiled split-K launch, a column-blocked one that must reduce at once) leave their
     partials pending and ONE launch finishes them -- every element summed as its own reduce kernel sums
-    it: bitwise equal to the immediate form.  Outside a window ``final`` changes nothing."""
+    it: bitwise equal to the immediate form.  Outside a window ``final`` changes nothing.  The other
+    four members of the family (fused norm backward, sparse, k4, k4 fused) the same way, every output
+    of theirs compared; each keeps (nb / ng) (p / 32) <= 112 partials per weight group (16, 64, 64, 64)."""
     from nesie_amd.kernels import HipKernels
     hip = _hip()
     g = torch.Generator(device=_dev()).manual_seed(11)
@@ -1030,6 +1032,102 @@ def test_deferred_weight_gradient_reductions_equal_the_immediate_ones_bit_for_bi
         HipKernels._deferred = None
     torch.cuda.synchronize()
     assert all(torch.equal(dw, want) for dw in outs)
+    # the other members: the same call outside a window and inside one, every output bit for bit
+    members = _deferral_members(hip, g)
+    wants = [run(True) for run in members]              # no window open: immediate
+    assert _lib_pending() == 0
+    HipKernels.begin_deferred_reductions()
+    try:
+        gots = []
+        for run in members:
+            before = _lib_pending()
+            gots.append(run(True))
+            assert _lib_pending() == before + 1
+        done = HipKernels.flush_deferred_reductions(close=True)
+    finally:
+        HipKernels._deferred = None
+    torch.cuda.synchronize()
+    assert len(done) == len(members) and _lib_pending() == 0
+    for got_m, want_m in zip(gots, wants):
+        assert len(got_m) == len(want_m)
+        for a, b in zip(got_m, want_m):
+            assert torch.equal(a, b)
+
+
+def _deferral_members(hip, g):
+    """-> one callable per weight-gradient method beside ``pw_wgrad``; run(final) makes the call into
+    fresh outputs and returns them (the weight gradient first, pre-filled with NaN)."""
+    dev = _dev()
+    rn = lambda *shape: torch.randn(*shape, device=dev, generator=g)  # noqa: E731
+
+    def folded(z, gamma, beta, ng):
+        nb, c, p = z.shape
+        zd = z.double().view(nb // ng, ng, c, p)
+        mean, invstd = zd.mean((0, 3)), (zd.var((0, 3), unbiased=False) + 1e-5).rsqrt()
+        scale = gamma.double().view(ng, c) * invstd
+        return torch.stack([scale, beta.double().view(ng, c) - mean * scale, mean, invstd], -1).view(ng * c, 4).float().contiguous()
+
+    def sums(da, z, zcoef, ng):           # (sum g, sum g zhat) per channel, one slot
+        nb, c, p = z.shape
+        cf = zcoef.view(ng, c, 4)[torch.arange(nb, device=dev) % ng]
+        gg = torch.where(torch.addcmul(cf[:, :, 1:2], z, cf[:, :, 0:1]) > 0, da, torch.zeros_like(da)).double()
+        zhat = (z.double() - cf[:, :, 2:3].double()) * cf[:, :, 3:4].double()
+        red = lambda t: t.view(nb // ng, ng, c, p).sum((0, 3))  # noqa: E731
+        return torch.stack([red(gg), red(gg * zhat)], -1).view(ng * c, 1, 2).float().contiguous()
+
+    # pw_wgrad_bn_backward, dz written over da
+    nb, ng, co, ci, p = 4, 2, 128, 128, 256
+    da, z, x = rn(nb, co, p), rn(nb, co, p) * 1.5 + 0.7, rn(nb, ci, p)
+    gamma, beta = rn(ng * co), rn(ng * co) * 0.3
+    xcoef = torch.rand(ng * ci, 4, device=dev, generator=g) + 0.5
+    xcoef[:, 1] -= 1.0
+    zcoef = folded(z, gamma, beta, ng)
+    part = sums(da, z, zcoef, ng)
+
+    def bn_backward(final):
+        src, dw = da.clone(), torch.full((ng, co, ci), float('nan'), device=dev)
+        dgamma, dbeta = torch.empty(ng * co, device=dev), torch.empty(ng * co, device=dev)
+        hip.pw_wgrad_bn_backward(src, z, zcoef, gamma, part, x, src, dw, dgamma, dbeta, ng=ng, x_coef=xcoef, final=final)
+        return dw, src, dgamma, dbeta
+
+    # pw_wgrad_sparse: 128 x 256 over 1024 positions, entries of a max over groups of 16
+    snb, sng, sp, ns = 4, 2, 1024, 16
+    assert hip.pw_wgrad_sparse_supported(128, 256, sp, ns)
+    ent = hip.pool_tail_pack(rn(snb, 128, sp // ns),
+                             torch.randint(0, ns, (snb, 128, sp // ns), device=dev, generator=g).to(torch.uint8))
+    sx = rn(snb, 256, sp)
+    scoef = torch.rand(sng * 256, 4, device=dev, generator=g) + 0.5
+    scoef[:, 1] -= 1.0
+
+    def sparse(final):
+        dw = torch.full((sng, 128, 256), float('nan'), device=dev)
+        hip.pw_wgrad_sparse(ent, ns, sx, dw, ng=sng, x_coef=scoef, final=final)
+        return (dw,)
+
+    # the k4 pair: 64 x 64 over an operand rebuilt from x4
+    knb, kp = 2, 1024
+    x4 = rn(knb, 4, kp) * 0.5
+    x4[:, 3] = x4[:, 3].abs() + 0.5
+    w0, w1 = rn(64, 4) * 0.5, rn(64, 64) * 0.2
+    kda, z1 = rn(knb, 64, kp), rn(knb, 64, kp)
+    gamma1 = torch.rand(64, device=dev, generator=g) + 0.5
+    coef0 = folded(torch.einsum('cj,njp->ncp', w0, x4), torch.rand(64, device=dev, generator=g) + 0.5, rn(64) * 0.3, 1)
+    coef1 = folded(z1, gamma1, rn(64) * 0.3, 1)
+    part1 = sums(kda, z1, coef1, 1)
+
+    def k4(final):
+        d, dw = kda.clone(), torch.full((64, 64), float('nan'), device=dev)
+        hip.pw_wgrad_bn_backward_k4(d, z1, coef1, gamma1, part1, x4, w0, coef0, dw, torch.empty(64, device=dev),
+                                    torch.empty(64, device=dev), final=final)
+        return (dw,)
+
+    def k4_fused(final):
+        dw = torch.full((64, 64), float('nan'), device=dev)
+        in_part, in_gpart = hip.pw_wgrad_bn_backward_k4_fused(kda.clone(), z1, coef1, gamma1, part1, x4, w0, coef0, w1, dw,
+                                                              torch.empty(64, device=dev), torch.empty(64, device=dev),
+                                                              final=final)
+        return dw, in_part, in_gpart
+    return [bn_backward, sparse, k4, k4_fused]
 
 
 def _lib_pending():
