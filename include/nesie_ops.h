@@ -300,6 +300,31 @@ int nesie_blend_conv_backward_staged(int b, int c, int m, int n, const float *dy
                                      const float *weight, const float *rel, float *d_table,
                                      float *d_wx, int segs, int seg_len, void *workspace,
                                      size_t workspace_bytes, void *stream);
+/* The same backward for ANY shape, without float atomics: any c >= 1 (no 64-channel blocks, no
+ * upper bound), any number of queries per face, any m >= 1, any pitch >= (segs - 1) * seg_off + c
+ * (no multiple of 4, no alignment beyond a float's), segs >= 1; b = 0 is a no-op, n = 0 writes
+ * zeros.  dy (B, segs, c, n/segs), idx / weight / rel (B, n, 3) in (proposal, face, grid point)
+ * order; idx values outside [0, m) are clamped as the forward clamps them.  z / bnb both NULL:
+ * plain backward; both given: the norm backward on the load (as nesie_blend_conv_backward_bn).
+ * A transposing pass stores dZ^T (B, segs, n/segs, c) query-major, nesie_inverted_index sorts the
+ * scene's 3n taps by seed, and one wave per (scene, face, seed, 256 channels) WRITES
+ *     d_table[b, j, s * seg_off + ch] = sum over the taps (p, t) of face s with idx[b, p, t] = j,
+ *                                       in ASCENDING tap position 3p + t, of weight[b,p,t] * dZ[p, ch]
+ * starting from 0 (the product rounded, then added): every element of the columns
+ * [s * seg_off, + c), s < segs, of every row is written exactly once (zero for a seed without
+ * taps), so with seg_off == c or segs == 1 the caller need not clear d_table.
+ * d_wx (segs, c, 3) (NULL = skip) is WRITTEN with the final sum of dy x rel: per (scene, run of
+ * 1024 queries of a face) the queries in four interleaved groups of 16 per 64-tile, ascending, the
+ * groups added as (0 + 1) + (2 + 3), then the partials in ascending (scene, run) order.
+ * Both orders depend on the shape and idx alone: two launches give the same bits.
+ * workspace: nesie_blend_conv_backward_any_workspace_bytes(b, c, m, n, segs) bytes, 4-byte aligned;
+ * no host synchronisation, so the launch sequence captures into a graph. */
+size_t nesie_blend_conv_backward_any_workspace_bytes(int b, int c, int m, int n, int segs);
+int nesie_blend_conv_backward_any(int b, int c, int m, int n, const float *dy, const float *z,
+                                  const float *bnb, int pitch, int seg_off, const int *idx,
+                                  const float *weight, const float *rel, float *d_table,
+                                  float *d_wx, int segs, int seg_len, void *workspace,
+                                  size_t workspace_bytes, void *stream);
 /* out[g * c + ch] = sum over the batch entries n = g (mod ng) and the p positions of x[n][ch][pos];
  * x (nb, c, p) with batch stride x_bstride >= c * p (a channel slice of a wider tensor is fine).
  * The bias gradient of a convolution without a norm behind it (autograd's grad.sum((0, 2)) for the

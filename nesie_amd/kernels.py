@@ -82,6 +82,20 @@ def _workspace(need, device):
     return torch.empty(max(need, 16), dtype=torch.uint8, device=device)
 
 
+def blend_backward_form(c, per_seg, m, deterministic):
+    """Which blend backward serves c channels, per_seg queries per face and m seeds:
+    'staged' (nesie_blend_conv_backward_staged: the 64 x 64-tile shapes, c in 64..256 step 64, whole
+    64-query tiles per face, at most 2047 seeds; fixed order), 'atomic' (the same tile shapes with
+    float atomics, when the deterministic backward is off) or 'any' (nesie_blend_conv_backward_any:
+    everything else, in both modes; fixed order)."""
+    tile = c % 64 == 0 and 64 <= c <= 256 and per_seg > 0 and per_seg % 64 == 0
+    if not tile:
+        return 'any'
+    if not deterministic:
+        return 'atomic'
+    return 'staged' if m + 1 <= 2048 else 'any'
+
+
 class HipKernels:
     """libnesie_hip.so, asynchronous on torch's current HIP stream."""
 
@@ -497,7 +511,9 @@ class HipKernels:
     # ``set_deterministic(False)`` restores the reference's atomicAdd scatters,
     # three_interpolate_cuda.cu:61-84, group_points_cuda.cu:10-31): every scatter-add of the backward
     # pass runs in an order fixed by the indices alone --
-    #  * the blend backward stages its rows and gathers them per seed (nesie_blend_conv_backward_staged);
+    #  * the blend backward stages its rows and gathers them per seed (nesie_blend_conv_backward_staged),
+    #    or, for the shapes the tile kernels do not take, sums each seed's taps through an inverted
+    #    index (nesie_blend_conv_backward_any; ``blend_backward_form`` chooses);
     #  * group_points / QueryAndGroup / gather_points / three_interpolate backward go through an
     #    inverted index of their indices (``scatter_index``), built on the spot when the caller did
     #    not hand one over (any number of source points);
@@ -518,18 +534,19 @@ class HipKernels:
         return self.inverted_index(idx.contiguous(), n)
 
     def blend_backward_writes_table(self, c, n, segs, m):
-        """True when ``blend_conv_backward`` WRITES d_table in full (the staged form): the caller
-        then need not zero it."""
-        return self.DETERMINISTIC and c % 64 == 0 and c <= 256 and (n // segs) % 64 == 0 and m + 1 <= 2048
+        """True when ``blend_conv_backward`` WRITES d_table in full (the staged and the general
+        form): the caller then need not zero it."""
+        return blend_backward_form(c, n // segs, m, self.DETERMINISTIC) != 'atomic'
 
     def blend_conv_backward(self, dy, seg_off, idx, weight, rel, d_table, d_wx, segs, seg_len,
                             bn_z=None, bnb=None):
         """dy (B, segs, c, n/segs) -> d_table (B, M, pitch) columns [s*seg_off, +c) and
         sum(dy x rel) WRITTEN to d_wx (segs, c, 3).  bn_z / bnb: dy is the gradient of
         relu(bn(bn_z)) and the norm backward runs on the tile load (bnb (segs*c, 8) from
-        ``pw_bnb_coef``).  Staged form (``blend_backward_writes_table``): no float atomics, d_table
-        written in full, bitwise reproducible (nesie_blend_conv_backward_staged); otherwise rows
-        are ADDED into d_table (zeroed by the caller) with atomics."""
+        ``pw_bnb_coef``).  ``blend_backward_form`` chooses: the staged form and the general form
+        (nesie_blend_conv_backward_staged / _any; ``blend_backward_writes_table``) use no float
+        atomics, write d_table in full and are bitwise reproducible; the atomic form ADDS its rows
+        into d_table (zeroed by the caller)."""
         _check(dy, idx, weight, d_table); _f32(dy, weight, d_table); _i32(idx)
         b, m, pitch = d_table.shape
         n, c = idx.shape[1], dy.shape[2]
@@ -537,19 +554,19 @@ class HipKernels:
         if d_wx is not None:
             _check(rel, d_wx); _f32(rel, d_wx)
             assert tuple(d_wx.shape) == (segs, c, 3)
+        if bnb is not None:
+            _check(bn_z, bnb); _f32(bn_z, bnb)
+            assert tuple(bn_z.shape) == tuple(dy.shape) and tuple(bnb.shape) == (segs * c, 8)
+        form = blend_backward_form(c, n // segs, m, self.DETERMINISTIC)
+        if form == 'any':
+            self.blend_conv_backward_any(dy, seg_off, idx, weight, rel, d_table, d_wx, segs, seg_len,
+                                         bn_z=bn_z, bnb=bnb)
+            return
         part = None
         if d_wx is not None:   # one partial per workgroup, summed here
             runs = _lib.load().nesie_blend_conv_runs(n, segs)
             part = torch.empty(b * runs, segs, c, 3, dtype=torch.float32, device=dy.device)
-        if bnb is not None:
-            _check(bn_z, bnb); _f32(bn_z, bnb)
-            assert tuple(bn_z.shape) == tuple(dy.shape) and tuple(bnb.shape) == (segs * c, 8)
-        if self.DETERMINISTIC and not self.blend_backward_writes_table(c, n, segs, m):
-            raise RuntimeError(
-                f'blend_conv_backward: no fixed-order form for c={c}, {n // segs} queries per face, '
-                f'{m} seeds (needs c in 64..256 step 64, faces of whole 64-query tiles, <= 2047 '
-                'seeds); HipKernels.set_deterministic(False) selects the atomic scatter')
-        if self.blend_backward_writes_table(c, n, segs, m):
+        if form == 'staged':
             assert seg_off == c or segs == 1, 'staged form: one column block per face'
             need = _lib.load().nesie_blend_conv_backward_workspace_bytes(b, c, n, segs)
             ws = torch.empty(need, dtype=torch.uint8, device=dy.device)
@@ -563,6 +580,22 @@ class HipKernels:
                     rel, d_table, part, segs, seg_len)
         if part is not None:      # (d_wx arrives zero-filled or empty from its caller: the sum overwrites it)
             torch.sum(part, 0, out=d_wx)
+
+    def blend_conv_backward_any(self, dy, seg_off, idx, weight, rel, d_table, d_wx, segs, seg_len,
+                                bn_z=None, bnb=None):
+        """``blend_conv_backward`` by the general form (nesie_blend_conv_backward_any): any c, any
+        number of queries per face, any seed count, any pitch; no float atomics, every d_table
+        element summed in ascending tap order and written once, d_wx written with the final sum."""
+        _check(dy, idx, weight, d_table); _f32(dy, weight, d_table); _i32(idx)
+        b, m, pitch = d_table.shape
+        n, c = idx.shape[1], dy.shape[2]
+        assert tuple(dy.shape) == (b, segs, c, n // segs)
+        if pitch != (segs - 1) * seg_off + c or not (seg_off == c or segs == 1):
+            d_table.zero_()       # (columns between or behind the faces' blocks: not the kernel's)
+        need = _lib.load().nesie_blend_conv_backward_any_workspace_bytes(b, c, m, n, segs)
+        ws = _workspace(need, dy.device)
+        _launch("nesie_blend_conv_backward_any", dy, b, c, m, n, dy, bn_z, bnb, pitch, seg_off, idx,
+                weight, rel, d_table, d_wx, segs, seg_len, ws, need)
 
     def three_interpolate_grad_wrapper(self, b, c, n, m, grad_out, idx, weight,
                                        grad_points):
