@@ -100,6 +100,22 @@ int nesie_head_loss_forward_sigma(int sigma_mode, int b, int k, int t, int c, co
                                   float *s_side_pred, int *sem_pick, int *kstar, float *dmin,
                                   float *partial, int *ticket, void *stream);
 
+/* nesie_head_loss_forward_sigma (sigma_mode 0: nesie_head_loss_forward) for a head whose IoU term
+ * is built on another IoU than the IoU-quality label: the IoU term and its gradient s_iou read iou
+ * (B*K), the label of the plain proposals' IoU-quality term reads iou_label (B*K) (the jittered
+ * proposals' label is iou_j as before).  IoU3DLoss(with_yaw=False), iou3d_loss.py:21-35,72-75: the
+ * loss is the axis-aligned IoU, the label stays the rotated one (nesie_head.py:372-373). */
+int nesie_head_loss_forward_label(int sigma_mode, int b, int k, int t, int c, const float *cls,
+                                  const float *bbox, const float *surface, const float *side,
+                                  const float *iou_s, const float *iou, const float *iou_label,
+                                  const float *iou_j, const long long *obj_t, const long long *label,
+                                  const float *obj_w, const float *box_w, const float *bbox_t,
+                                  const float *centre_t, const float *valid_w, const float *config,
+                                  float *loss, float *s_cls, float *s_centre, float *s_surface,
+                                  float *s_iou, float *s_iou_s, float *s_side_surf,
+                                  float *s_side_iou, float *s_side_pred, int *sem_pick, int *kstar,
+                                  float *dmin, float *partial, int *ticket, void *stream);
+
 /* The SAQE head's ADDITIONAL supervised terms (saqe_head.py:331-521 `loss`, :524-703 `sup_loss`):
  *   loss[0] = 0.5 (CE(R_obj) + CE(R_obj_jitter)), class- and proposal-weighted like the objectness term;
  *   loss[1] = sum box_w * w_angle * (SmoothL1(sin th - sin th*) + SmoothL1(cos th - cos th*)), in

@@ -407,6 +407,33 @@ int nesie_iou3d_forward(int n, const float *box1, const float *box2, float *iou,
 int nesie_giou3d_forward(int n, const float *box1, const float *box2, int kind, int enclosing,
                          float *loss, float *iou, float *jac, void *stream);
 
+/* mmdet3d/core/bbox/iou_calculators/iou3d_calculator.py:201-320  axis_aligned_bbox_overlaps_3d
+ * (AxisAlignedBboxOverlaps3D :170-198; the loss of models/losses/axis_aligned_iou_loss.py:9-25 and
+ * of iou3d_loss.py:21-35 is 1 - the paired form).  Boxes are corners (x1, y1, z1, x2, y2, z2), f32,
+ * rows 8-byte aligned.  mode 0: IoU = overlap / max(area1 + area2 - overlap, eps), overlap the
+ * product of clamp(min(hi) - max(lo), 0); mode 1: GIoU = IoU - (enclose - union) / enclose with
+ * enclose = max(prod(clamp(max(hi) - min(lo), 0)), eps).  Same operations in the same order as the
+ * reference, products and sums rounded separately.  Derivatives are those torch autograd takes of
+ * that function: clamp(x, 0) passes the gradient where x >= 0 (x == 0 included), a max / min of two
+ * equal arguments gives each side one half, max(., eps) likewise.
+ *   paired  (is_aligned=True) : out[n]; jac1[n,6] = d out / d box1, jac2[n,6] = d out / d box2,
+ *           either may be NULL.
+ *   matrix  (is_aligned=False): box1 (b,m,6), box2 (b,n,6), out (b,m,n); the reference's leading
+ *           batch dimensions flattened to b.
+ *   matrix backward: grad1 (b,m,6) = sum over n, grad2 (b,n,6) = sum over m of grad_out (b,m,n)
+ *           times the recomputed Jacobian, either may be NULL; every sum runs in a fixed order
+ *           (lane-strided partials, then a fixed tree), without atomics: the same bits every run.
+ * A negative size, a mode outside {0, 1}, or a null box1 / box2 / out / grad_out (or a row pointer
+ * that is not 8-byte aligned) with a positive count is NESIE_ERR_INVALID_ARG; n == 0 (matrix:
+ * b * m * n == 0) succeeds without a launch and touches nothing. */
+int nesie_aa_iou3d_paired_forward(int n, const float *box1, const float *box2, int mode, float eps,
+                                  float *out, float *jac1, float *jac2, void *stream);
+int nesie_aa_iou3d_matrix_forward(int b, int m, int n, const float *box1, const float *box2,
+                                  int mode, float eps, float *out, void *stream);
+int nesie_aa_iou3d_matrix_backward(int b, int m, int n, const float *box1, const float *box2,
+                                   int mode, float eps, const float *grad_out, float *grad1,
+                                   float *grad2, void *stream);
+
 /* Training-mode BatchNorm with an optional fused ReLU over x[B, C, P] (statistics per
  * channel over B*P; biased variance for normalisation, unbiased for running_var, as
  * torch.nn.BatchNorm{1,2}d).  No extension entry in the reference: it builds

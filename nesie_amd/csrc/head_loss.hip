@@ -108,7 +108,9 @@ __global__ __launch_bounds__(HL_BLOCK) void head_targets_kernel(
 struct HeadLoss {
   int b, k, t, c;
   const float *cls, *bbox, *surface, *side, *iou_s;
-  const float *iou;        // (B*K) IoU of the predicted box with its target
+  const float *iou;        // (B*K) IoU of the predicted box with its target: the IoU term reads it
+  const float *iou_label;  // (B*K) the IoU-quality label of the predicted box (== iou unless the IoU
+                           // term is built on another IoU than the label's, nesie_head_loss_forward_label)
   const float *iou_j;      // (B*K) IoU of the jittered box with its target
   // targets (head_targets_kernel)
   const long long *obj_t, *label;
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(HL_PB) void head_loss_kernel(const HeadLoss a) {
       const size_t row = ((size_t)bi * 2 * K + (size_t)hj * K + kk) * C;
       const float *pr = a.iou_s + row;
       float *dp = a.s_iou_s + row;
-      const float score = hj ? a.iou_j[p] : a.iou[p];
+      const float score = hj ? a.iou_j[p] : a.iou_label[p];
       float acc = 0.f;
       if (unsup) {
         for (int j = 0; j < C; ++j) dp[j] = 0.f;
@@ -525,7 +527,7 @@ extern "C" int nesie_head_targets(int b, int k, int t, const float *agg, const f
 }
 
 static int head_loss_forward_impl(
-    const char *W, const float *quality, int flags,
+    const char *W, const float *quality, int flags, const float *iou_label /* NULL: iou */,
     int b, int k, int t, int c, const float *cls, const float *bbox, const float *surface,
     const float *side, const float *iou_s, const float *iou, const float *iou_j,
     const long long *obj_t, const long long *label, const float *obj_w, const float *box_w,
@@ -546,6 +548,7 @@ static int head_loss_forward_impl(
   a.b = b; a.k = k; a.t = t; a.c = c;
   a.cls = cls; a.bbox = bbox; a.surface = surface; a.side = side; a.iou_s = iou_s;
   a.iou = iou; a.iou_j = iou_j;
+  a.iou_label = iou_label ? iou_label : iou;
   a.obj_t = obj_t; a.label = label; a.obj_w = obj_w; a.box_w = box_w; a.bbox_t = bbox_t;
   a.centre_t = centre_t; a.valid_w = valid_w;
   a.alpha = config[0]; a.w_obj = config[1]; a.cw0 = config[2]; a.cw1 = config[3];
@@ -571,7 +574,7 @@ extern "C" int nesie_head_loss_forward(
     float *s_surface, float *s_iou, float *s_iou_s, float *s_side_surf, float *s_side_iou,
     float *s_side_pred, int *sem_pick, int *kstar, float *dmin, float *partial, int *ticket,
     void *stream) {
-  return head_loss_forward_impl("head_loss_forward", nullptr, 0, b, k, t, c, cls, bbox, surface, side, iou_s,
+  return head_loss_forward_impl("head_loss_forward", nullptr, 0, nullptr, b, k, t, c, cls, bbox, surface, side, iou_s,
                                 iou, iou_j, obj_t, label, obj_w, box_w, bbox_t, centre_t, valid_w, config,
                                 loss, s_cls, s_centre, s_surface, s_iou, s_iou_s, s_side_surf, s_side_iou,
                                 s_side_pred, sem_pick, kstar, dmin, partial, ticket, stream);
@@ -590,10 +593,30 @@ extern "C" int nesie_head_loss_forward_sigma(
   const char *W = "head_loss_forward_sigma";
   NESIE_REQUIRE(sigma_mode >= 0 && sigma_mode <= 2, W);
   const int flags = sigma_mode == 1 ? HL_DETACH_SIGMA : sigma_mode == 2 ? HL_NO_SIGMA : 0;
-  return head_loss_forward_impl(W, nullptr, flags, b, k, t, c, cls, bbox, surface, side, iou_s,
+  return head_loss_forward_impl(W, nullptr, flags, nullptr, b, k, t, c, cls, bbox, surface, side, iou_s,
                                 iou, iou_j, obj_t, label, obj_w, box_w, bbox_t, centre_t, valid_w, config,
                                 loss, s_cls, s_centre, s_surface, s_iou, s_iou_s, s_side_surf, s_side_iou,
                                 s_side_pred, sem_pick, kstar, dmin, partial, ticket, stream);
+}
+
+extern "C" int nesie_head_loss_forward_label(
+    int sigma_mode, int b, int k, int t, int c, const float *cls, const float *bbox,
+    const float *surface, const float *side, const float *iou_s, const float *iou,
+    const float *iou_label, const float *iou_j,
+    const long long *obj_t, const long long *label, const float *obj_w, const float *box_w,
+    const float *bbox_t, const float *centre_t, const float *valid_w,
+    const float *config /* [11] */, float *loss, float *s_cls, float *s_centre,
+    float *s_surface, float *s_iou, float *s_iou_s, float *s_side_surf, float *s_side_iou,
+    float *s_side_pred, int *sem_pick, int *kstar, float *dmin, float *partial, int *ticket,
+    void *stream) {
+  const char *W = "head_loss_forward_label";
+  NESIE_REQUIRE(sigma_mode >= 0 && sigma_mode <= 2, W);
+  NESIE_REQUIRE(b <= 0 || iou_label, W);
+  const int flags = sigma_mode == 1 ? HL_DETACH_SIGMA : sigma_mode == 2 ? HL_NO_SIGMA : 0;
+  return head_loss_forward_impl(W, nullptr, flags, iou_label, b, k, t, c, cls, bbox, surface, side,
+                                iou_s, iou, iou_j, obj_t, label, obj_w, box_w, bbox_t, centre_t, valid_w,
+                                config, loss, s_cls, s_centre, s_surface, s_iou, s_iou_s, s_side_surf,
+                                s_side_iou, s_side_pred, sem_pick, kstar, dmin, partial, ticket, stream);
 }
 
 extern "C" int nesie_head_loss_forward_unsup(
@@ -607,7 +630,7 @@ extern "C" int nesie_head_loss_forward_unsup(
     void *stream) {
   const char *W = "head_loss_forward_unsup";
   NESIE_REQUIRE(b == 0 || quality, W);
-  return head_loss_forward_impl(W, quality, HL_UNSUP | (detach_sigma ? HL_DETACH_SIGMA : 0), b, k, t, c, cls,
+  return head_loss_forward_impl(W, quality, HL_UNSUP | (detach_sigma ? HL_DETACH_SIGMA : 0), nullptr, b, k, t, c, cls,
                                 bbox, surface, side, iou_s, iou, iou, obj_t, label, obj_w, box_w, bbox_t,
                                 centre_t, valid_w, config, loss, s_cls, s_centre, s_surface, s_iou, s_iou_s,
                                 s_side_surf, s_side_iou, s_side_pred, sem_pick, kstar, dmin, partial, ticket,

@@ -706,6 +706,44 @@ class HipKernels:
         _launch("nesie_giou3d_forward", box1, n, box1, box2, int(kind), int(enclosing), loss, iou,
                 jac)
 
+    @staticmethod
+    def _aa_rows(count, *named):
+        """Each (name, tensor or None, rows) of an axis-aligned IoU launch: a device f32 tensor of
+        rows x 6 whose rows can be read as 8-byte pairs."""
+        for name, t, rows in named:
+            if t is None:
+                continue
+            _check(t); _f32(t)
+            assert t.numel() == count * rows * 6, (name, tuple(t.shape), count, rows)
+            assert t.data_ptr() % 8 == 0, f'{name}: rows must be 8-byte aligned'
+
+    def aa_iou3d_paired_forward(self, box1, box2, mode, eps, out, jac1=None, jac2=None):
+        """box1, box2 (n,6) corners; mode 0 IoU / 1 GIoU; out (n,); jac1, jac2 (n,6) = d out / d box1,
+        d out / d box2, or None (nesie_aa_iou3d_paired_forward)."""
+        _check(out); _f32(out)
+        n = out.numel()
+        self._aa_rows(1, ('box1', box1, n), ('box2', box2, n), ('jac1', jac1, n), ('jac2', jac2, n))
+        _launch("nesie_aa_iou3d_paired_forward", box1, n, box1, box2, int(mode), float(eps), out,
+                jac1, jac2)
+
+    def aa_iou3d_matrix_forward(self, box1, box2, mode, eps, out):
+        """box1 (b,m,6), box2 (b,n,6) corners; out (b,m,n) (nesie_aa_iou3d_matrix_forward)."""
+        _check(out); _f32(out)
+        b, m, n = out.shape
+        self._aa_rows(b, ('box1', box1, m), ('box2', box2, n))
+        _launch("nesie_aa_iou3d_matrix_forward", box1, b, m, n, box1, box2, int(mode), float(eps),
+                out)
+
+    def aa_iou3d_matrix_backward(self, box1, box2, mode, eps, grad_out, grad1=None, grad2=None):
+        """grad_out (b,m,n) -> grad1 (b,m,6) and / or grad2 (b,n,6), in a fixed summation order
+        (nesie_aa_iou3d_matrix_backward)."""
+        _check(grad_out); _f32(grad_out)
+        b, m, n = grad_out.shape
+        self._aa_rows(b, ('box1', box1, m), ('box2', box2, n), ('grad1', grad1, m),
+                      ('grad2', grad2, n))
+        _launch("nesie_aa_iou3d_matrix_backward", box1, b, m, n, box1, box2, int(mode), float(eps),
+                grad_out, grad1, grad2)
+
     def conv_wgrad(self, dy, x, dw, x_coef=None, x_relu=False, bn_z=None, bnb=None):
         """dw (cout, cin) = sum_b dy[b] (cout, P) @ act(x[b]) (cin, P)^T on the matrix cores;
         dy and x may be batch-strided views (each dy[b], x[b] contiguous).  bn_z / bnb: dy is the
@@ -1175,12 +1213,14 @@ class HipKernels:
         return out
 
     def head_loss_forward(self, cls, bbox, surface, side, iou_s, iou, iou_j, tg, config, ticket,
-                          quality=None, detach_sigma=False, sigma_mode=0):
+                          quality=None, detach_sigma=False, sigma_mode=0, iou_label=None):
         """The seven loss terms + their saved gradients (nesie_head_loss_forward).  cls
         (B,2+C,K), bbox (B,K,7), surface (B,K,6), side (6,B,C,2K), iou_s (B,2K,C), iou / iou_j
         (B*K); tg = head_targets(...); config = 11 python floats; ticket = a zeroed int32 scalar
         that lives outside any graph capture (the kernel leaves it zero).  -> (loss (7,), saved dict).
-        quality (B*K, 6): the unsupervised variant (nesie_head_loss_forward_unsup; iou_j unused)."""
+        quality (B*K, 6): the unsupervised variant (nesie_head_loss_forward_unsup; iou_j unused).
+        iou_label (B*K): the plain proposals' IoU-quality label where it is not ``iou`` itself
+        (nesie_head_loss_forward_label; the unsupervised variant has no such term)."""
         _check(cls, bbox, surface, side, iou_s, iou, iou_j)
         _f32(cls, bbox, surface, side, iou_s, iou, iou_j)
         b, nc, k = cls.shape
@@ -1204,6 +1244,11 @@ class HipKernels:
             assert quality.numel() == b * k * 6
             head = ("nesie_head_loss_forward_unsup", cls, b, k, t, c, cls, bbox, surface, side, iou_s,
                     iou, quality, bool(detach_sigma))
+        elif iou_label is not None:
+            _check(iou_label); _f32(iou_label)
+            assert iou_label.numel() == b * k
+            head = ("nesie_head_loss_forward_label", cls, int(sigma_mode), b, k, t, c, cls, bbox,
+                    surface, side, iou_s, iou, iou_label, iou_j)
         elif sigma_mode:      # the SAQE head's supervised losses: constant (1) or no (2) uncertainties
             head = ("nesie_head_loss_forward_sigma", cls, int(sigma_mode), b, k, t, c, cls, bbox,
                     surface, side, iou_s, iou, iou_j)

@@ -4,6 +4,7 @@ the reference's ``__all__`` (voxel / spconv / paconv / iou3d / roi-aware
 pooling ...) resolves to stubs that raise on use, so ``from mmdet3d.ops import X``
 style code keeps importing ("import-time requirement").
 """
+from .axis_aligned_iou import AxisAlignedBboxOverlaps3D, axis_aligned_bbox_overlaps_3d
 from .ball_query import ball_query
 from .furthest_point_sample import (Points_Sampler, furthest_point_sample,
                                     furthest_point_sample_with_dist)
@@ -25,6 +26,7 @@ _HOT = [
     'points_in_boxes_batch', 'Points_Sampler', 'build_sa_module', 'cal_iou_3d', 'sort_v',
     'ConvModule', 'boxes_overlap_bev', 'points_in_boxes_count',
     'boxes_iou_bev', 'nms_gpu', 'nms_normal_gpu', 'knn', 'cal_giou_3d',
+    'AxisAlignedBboxOverlaps3D', 'axis_aligned_bbox_overlaps_3d',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',

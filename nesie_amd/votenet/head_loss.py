@@ -35,14 +35,18 @@ class HeadLossFn(Function):
 
     @staticmethod
     def forward(ctx, cls, bbox, surface, side_all, iou_all, iou, iou_j, targets, config, ticket,
-                quality=None, detach_sigma=False, sigma_mode=0):
+                quality=None, detach_sigma=False, sigma_mode=0, iou_label=None):
         """quality (B, K, 6): the unsupervised variant -- semantic, centre, surface and IoU terms
-        with the pseudo labels' side qualities in the weights, the other three terms zero."""
+        with the pseudo labels' side qualities in the weights, the other three terms zero.
+        iou_label (B, K), no gradient: the IoU-quality label of the plain proposals where the IoU
+        term is built on another IoU (``IoU3DLoss(with_yaw=False)``); None: ``iou`` is both."""
         backend = backend_for(cls)
         loss, saved = backend.head_loss_forward(cls, bbox, surface, side_all, iou_all,
                                                 iou.reshape(-1), iou_j.reshape(-1), targets, config,
                                                 ticket, quality=quality, detach_sigma=detach_sigma,
-                                                sigma_mode=sigma_mode)
+                                                sigma_mode=sigma_mode,
+                                                iou_label=None if iou_label is None
+                                                else iou_label.reshape(-1))
         ctx.saved, ctx.label, ctx.k, ctx.iou_shape = saved, targets['mask_targets'], bbox.shape[1], iou.shape
         if sigma_mode:          # (the SAQE extras read the arg-max classes)
             ctx.mark_non_differentiable(saved['sem_pick'])
@@ -57,7 +61,7 @@ class HeadLossFn(Function):
         backend = backend_for(g)
         d = backend.head_loss_backward(g, ctx.label, ctx.saved, ctx.k)
         return (d['cls'], d['bbox'], d['surface'], d['side'], d['iou_s'],
-                d['iou'].view(ctx.iou_shape), None, None, None, None, None, None, None)
+                d['iou'].view(ctx.iou_shape), None, None, None, None, None, None, None, None)
 
 
 def config_of(head):

@@ -1,7 +1,7 @@
 """Losses of the Nesie head.
 
 Restates ``mmdet3d/models/losses/{chamfer_distance,surface_loss,side_pred_loss,
-iou3d_loss,gfocal_loss}.py`` and the mmdet 2.19 loss plumbing they call
+iou3d_loss,axis_aligned_iou_loss,gfocal_loss}.py`` and the mmdet 2.19 loss plumbing they call
 (``weighted_loss`` / ``weight_reduce_loss`` / MSE / L1 / SmoothL1 / CrossEntropy;
 source not in the reference tree, semantics from SURVEY.md appendix C).
 """
@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ..mmdet3d_ops.axis_aligned_iou import axis_aligned_bbox_overlaps_3d
 from ..mmdet3d_ops.rotated_iou import cal_diou_3d, cal_giou_3d, cal_iou_3d
 
 
@@ -190,11 +191,48 @@ class SidePredLoss(nn.Module):
         return self.loss_func(pred_side, label_side, weight, avg_factor, reduction_override)
 
 
-# ---- IoU3D (iou3d_loss.py:12-14, 38-76) -----------------------------------------
+# ---- axis-aligned IoU (axis_aligned_iou_loss.py:9-78, iou3d_loss.py:21-35) ----------------------
+def axis_aligned_iou_loss(pred, target):
+    """1 - IoU of one-to-one (…, 6) corner boxes (x1, y1, z1, x2, y2, z2) -> (…)."""
+    return 1 - axis_aligned_bbox_overlaps_3d(pred, target, is_aligned=True)
+
+
+def centre_size_to_corners(bbox):
+    """(…, >= 6) centre + size (+ heading, ignored) -> (…, 6) corners (iou3d_loss.py:23-31)."""
+    return torch.stack((bbox[..., 0] - bbox[..., 3] / 2, bbox[..., 1] - bbox[..., 4] / 2,
+                        bbox[..., 2] - bbox[..., 5] / 2, bbox[..., 0] + bbox[..., 3] / 2,
+                        bbox[..., 1] + bbox[..., 4] / 2, bbox[..., 2] + bbox[..., 5] / 2), dim=-1)
+
+
+class AxisAlignedIoULoss(nn.Module):
+    """1 - IoU of corner boxes, weighted and reduced (axis_aligned_iou_loss.py:28-78)."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert reduction in ['none', 'sum', 'mean']
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None,
+                **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        loss = axis_aligned_iou_loss(pred, target)
+        if weight is not None and reduction != 'none':
+            # reference :70-72 returns (pred * weight).sum() (== 0) when no weight is positive;
+            # as IoU3DLoss: masking the unweighted entries gives that zero without the host sync
+            loss = torch.where(weight > 0, loss, torch.zeros_like(loss))
+        return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+# ---- IoU3D (iou3d_loss.py:12-14, 21-35, 38-76) --------------------------------------------------
 class IoU3DLoss(nn.Module):
+    """with_yaw: 1 - rotated IoU of (…, 7) boxes; without: 1 - axis-aligned IoU of (…, 7) or (…, 6)
+    centre + size boxes, the heading ignored (iou3d_loss.py:72-75)."""
+
     def __init__(self, with_yaw=True, reduction='mean', loss_weight=1.0):
         super().__init__()
-        assert with_yaw, 'axis-aligned IoU loss is not used by the shipped configs'
+        self.with_yaw = with_yaw
         self.reduction = reduction
         self.loss_weight = loss_weight
 
@@ -204,7 +242,11 @@ class IoU3DLoss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         if weight is not None and weight.dim() > 1:
             weight = weight.mean(-1)
-        loss = 1 - cal_iou_3d(pred[None, ...], target[None, ...])  # (1, N)
+        if self.with_yaw:
+            loss = 1 - cal_iou_3d(pred[None, ...], target[None, ...])  # (1, N)
+        else:
+            loss = axis_aligned_iou_loss(centre_size_to_corners(pred),
+                                         centre_size_to_corners(target))  # (N,)
         if weight is not None:
             # reference :53-54 returns pred.sum() * weight.sum() (== 0) when no weight is
             # positive; masking the unweighted entries gives the same zeros without the
@@ -290,6 +332,7 @@ class GeneralQualityFocalLoss(nn.Module):
 
 _LOSSES = dict(ChamferDistance=ChamferDistance, CrossEntropyLoss=CrossEntropyLoss,
                IoU3DLoss=IoU3DLoss, GIoU3DLoss=GIoU3DLoss, DIoU3DLoss=DIoU3DLoss,
+               AxisAlignedIoULoss=AxisAlignedIoULoss,
                GeneralQualityFocalLoss=GeneralQualityFocalLoss,
                SurfaceLoss=SurfaceLoss, SidePredLoss=SidePredLoss, MSELoss=MSELoss,
                L1Loss=L1Loss, SmoothL1Loss=SmoothL1Loss)

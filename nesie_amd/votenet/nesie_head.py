@@ -23,7 +23,8 @@ from ..mmdet3d_ops.rotated_iou import cal_iou_3d
 from .bbox_module import ReliableConvBboxHead
 from .boxes import DepthInstance3DBoxes, depth_to_lidar_boxes, depth_to_lidar_points
 from . import head_loss
-from .losses import build_loss
+from ..mmdet3d_ops.axis_aligned_iou import axis_aligned_bbox_overlaps_3d
+from .losses import build_loss, centre_size_to_corners
 from ..streams import fork_join
 from .side_pooling import SidePooling
 from .vote_module import VoteModule
@@ -475,9 +476,21 @@ class NesieHead(nn.Module):
             losses['targets'] = targets_b
         return losses
 
+    def _loss_iou(self, boxes, bbox_targets):
+        """-> (iou, label_iou) for the fused loss kernel.  iou (B, K), differentiable: the IoU
+        ``self.iou_loss`` is built on, rotated or (``with_yaw=False``) axis-aligned with the heading
+        ignored.  label_iou: the rotated IoU the IoU-quality term is supervised with whatever the
+        IoU loss is (reference :372), or None where ``iou`` is that number itself."""
+        if getattr(self.iou_loss, 'with_yaw', True):
+            return cal_iou_3d(boxes, bbox_targets), None
+        iou = axis_aligned_bbox_overlaps_3d(centre_size_to_corners(boxes),
+                                            centre_size_to_corners(bbox_targets), is_aligned=True)
+        return iou, cal_iou_3d(boxes.detach(), bbox_targets)
+
     def _fused_loss(self, bbox_preds, targets, ret_target):
         """The same eight terms with the seven per-proposal ones in one launch
-        (``head_loss.HeadLossFn``); the vote term and the two rotated-IoU evaluations stay."""
+        (``head_loss.HeadLossFn``); the vote term and the IoU evaluations stay (the quality label
+        of the jittered proposals is the rotated IoU whatever the IoU loss is)."""
         (vote_targets, vote_target_masks, center_targets, bbox_targets, mask_targets,
          valid_gt_masks, objectness_targets, objectness_weights, box_loss_weights,
          valid_gt_weights, assignment) = targets
@@ -485,7 +498,7 @@ class NesieHead(nn.Module):
             bbox_preds['seed_points'], bbox_preds['vote_points'], bbox_preds['seed_indices'],
             vote_target_masks, vote_targets)
         boxes = bbox_preds['bbox_preds']
-        iou = cal_iou_3d(boxes, bbox_targets)                              # (B, K), with gradient
+        iou, label_iou = self._loss_iou(boxes, bbox_targets)               # (B, K), with gradient
         iou_jitter = cal_iou_3d(bbox_preds['jitter_bbox_preds'], bbox_targets).detach()
         tg = dict(obj_targets=objectness_targets, mask_targets=mask_targets,
                   obj_weights=objectness_weights, box_weights=box_loss_weights,
@@ -495,7 +508,7 @@ class NesieHead(nn.Module):
             bbox_preds['_cls_all'].contiguous(), boxes.contiguous(),
             bbox_preds['surface_pred'].contiguous(), bbox_preds['_side_all'].contiguous(),
             bbox_preds['_iou_all'].contiguous(), iou, iou_jitter, tg, head_loss.config_of(self),
-            self._loss_ticket)
+            self._loss_ticket, None, False, 0, label_iou)
         losses = dict(vote_loss=vote_loss, **dict(zip(head_loss.TERMS, terms)))
         if ret_target:
             losses['targets'] = bbox_targets.view_as(boxes)
@@ -559,11 +572,11 @@ class NesieHead(nn.Module):
 
     def _fused_unsup_loss(self, bbox_preds, targets, pseudo_quality_side):
         """The four terms in one launch (``head_loss.HeadLossFn`` with the side qualities); the
-        rotated-IoU evaluation stays."""
+        IoU evaluation stays."""
         (_, _, center_targets, bbox_targets, mask_targets, _, objectness_targets,
          objectness_weights, box_loss_weights, valid_gt_weights, _) = targets
         boxes = bbox_preds['bbox_preds']
-        iou = cal_iou_3d(boxes, bbox_targets)                              # (B, K), with gradient
+        iou, _ = self._loss_iou(boxes, bbox_targets)                       # (B, K), with gradient
         tg = dict(obj_targets=objectness_targets, mask_targets=mask_targets,
                   obj_weights=objectness_weights, box_weights=box_loss_weights,
                   bbox_targets=bbox_targets, center_targets=center_targets,

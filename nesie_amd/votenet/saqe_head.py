@@ -195,7 +195,7 @@ class SAQEHead(NesieHead):
             bbox_preds['seed_points'], bbox_preds['vote_points'], bbox_preds['seed_indices'],
             vote_target_masks, vote_targets)
         boxes = bbox_preds['bbox_preds'].contiguous()
-        iou = cal_iou_3d(boxes, bbox_targets)                              # (B, K), with gradient
+        iou, label_iou = self._loss_iou(boxes, bbox_targets)               # (B, K), with gradient
         iou_jitter = cal_iou_3d(bbox_preds['jitter_bbox_preds'], bbox_targets).detach()
         tg = dict(obj_targets=objectness_targets, mask_targets=mask_targets,
                   obj_weights=objectness_weights, box_weights=box_loss_weights,
@@ -206,7 +206,7 @@ class SAQEHead(NesieHead):
         out = head_loss.HeadLossFn.apply(
             bbox_preds['_cls_all'].contiguous(), boxes, bbox_preds['surface_pred'].contiguous(),
             side_all, bbox_preds['_iou_all'].contiguous(), iou, iou_jitter, tg, base_cfg,
-            self._loss_ticket, None, False, 1 if sup else 2)
+            self._loss_ticket, None, False, 1 if sup else 2, label_iou)
         base, sem_pick = dict(zip(head_loss.TERMS, out[:7])), out[7]
         extra = dict(zip(head_loss.SAQE_TERMS, head_loss.SaqeExtraFn.apply(
             bbox_preds['_robj_all'].contiguous(), bbox_preds['_rot_all'].contiguous(), boxes, side_all,
