@@ -362,6 +362,61 @@ int nesie_points_in_boxes_batch(int b, int boxes_num, int pts_num,
                                 const float *boxes, const float *pts, int *out,
                                 void *stream);
 
+/* points_in_boxes_cuda.cu:51-77, :116-151  points_in_boxes_gpu
+ * (boxes[B,T,7], pts[B,M,3], out[B,M] i32): the index of the FIRST box of the scene that holds the
+ * point under the same test, else -1.  WRITTEN in full (the reference pre-fills -1), also with
+ * boxes_num == 0.  A negative size is NESIE_ERR_INVALID_ARG; b or pts_num == 0 succeeds without a
+ * launch. */
+int nesie_points_in_boxes_gpu(int b, int boxes_num, int pts_num, const float *boxes,
+                              const float *pts, int *out, void *stream);
+
+/* mmdet3d/ops/roiaware_pool3d/src/roiaware_pool3d_kernel.cu  roiaware_pool3d forward / backward
+ * (the size arguments in the order of its launchers, :228-275 / :343-364, plus pts_num and the
+ * membership table).
+ *   rois[N,7] LiDAR frame (x, y, z_bottom, w, l, h, rz), pts[P,3], pts_feature[P,C] fp32,
+ *   (out_x, out_y, out_z) each 1 .. 256, m = max_pts_each_voxel >= 1, pool_method 0 = max, 1 = avg.
+ * In-box test and local coordinates (:14-44): the test of nesie_points_in_boxes_batch, exactly --
+ *   cos / sin of (float)(rz + pi/2) evaluated in double and rounded to float, products and sums
+ *   fp32 without contraction, the z window |z - (z_bottom + h/2)| <= h/2 and the half extents
+ *   compared in double; x / y strict, z inclusive (csrc/pib_test.h is the one device copy).
+ * Voxel of an inside point (:65-78), all fp32 with IEEE division: x_res = l / out_x,
+ *   y_res = w / out_y, z_res = h / out_z; x_idx = trunc((local_x + l/2) / x_res),
+ *   y_idx = trunc((local_y + w/2) / y_res), z_idx = trunc((pts.z - rois.z) / z_res), each clamped
+ *   into [0, out - 1].
+ * Collection (:93-127): per voxel the inside points in ascending point index, only the first
+ *   m - 1 kept.  pts_idx_of_voxels[N,ox,oy,oz,m] i32: slot 0 = the kept count, slots 1 .. count =
+ *   the indices, the rest 0.  pts_voxel[N,P] i32 (no reference output; its pts_mask, :45-91, after
+ *   the capacity rule): the flat voxel (x_idx * oy + y_idx) * oz + z_idx in which the box KEEPS the
+ *   point, else -1.  The backward gathers through it; it may be null when no backward follows.
+ * Max pool (:129-187): per voxel and channel over the kept points in slot order with strict >
+ *   starting from -inf (the lowest index wins a tie); argmax[N,ox,oy,oz,C] = that point, -1 for a
+ *   voxel without a kept point (or none above -inf); pooled = the maximum, 0 where argmax == -1.
+ * Avg pool (:189-226): an fp32 running sum in slot order divided by the count; 0 for an empty
+ *   voxel; argmax is written 0 (the reference leaves its zero fill).
+ * pooled[N,ox,oy,oz,C], argmax, pts_idx_of_voxels and pts_voxel are WRITTEN in full.
+ * Backward (:277-341): max: grad_in[argmax, c] += grad_out; avg: grad_in[p, c] += grad_out *
+ *   (1 / max(count, 1)) for every kept point, the product rounded to fp32 before the add.  The
+ *   reference adds with float atomics; here every grad_in[p, c] is the sum of its contributions in
+ *   ascending (box, voxel) order, without contraction, by one thread: no float atomics in either
+ *   setting of the deterministic switch.  grad_in[P,C] is WRITTEN in full.
+ * No entry allocates, every launch goes on the given stream.  nesie_roiaware_pool3d_sizes:
+ *   out[0] = elements of pts_idx_of_voxels, out[1] = of pooled / argmax, out[2] = of pts_voxel.
+ * A negative size, m < 1 or another pool_method is NESIE_ERR_INVALID_ARG; an out_* outside
+ * 1 .. 256 NESIE_ERR_UNSUPPORTED.  N, P or C == 0 succeeds without a kernel launch and clears
+ * whatever output is not empty (zeros; pts_voxel -1). */
+int nesie_roiaware_pool3d_sizes(int boxes_num, int pts_num, int channels, int out_x, int out_y,
+                                int out_z, int max_pts_each_voxel, long long *out);
+int nesie_roiaware_pool3d_forward(int boxes_num, int pts_num, int channels,
+                                  int max_pts_each_voxel, int out_x, int out_y, int out_z,
+                                  const float *rois, const float *pts, const float *pts_feature,
+                                  int *argmax, int *pts_idx_of_voxels, float *pooled_features,
+                                  int *pts_voxel, int pool_method, void *stream);
+int nesie_roiaware_pool3d_backward(int boxes_num, int pts_num, int out_x, int out_y, int out_z,
+                                   int channels, int max_pts_each_voxel,
+                                   const int *pts_idx_of_voxels, const int *argmax,
+                                   const int *pts_voxel, const float *grad_out, float *grad_in,
+                                   int pool_method, void *stream);
+
 /* Max over the neighbourhood axis of a grouped tensor: x[rows, nsample] -> out[rows],
  * argmax[rows] (one byte, smallest index on ties).  No extension entry in the reference:
  * it calls ATen's F.max_pool2d(kernel=[1, nsample]) (point_sa_module.py:149-150) and

@@ -9,19 +9,13 @@
 // cosf/sinf lie within their own 2-ulp error of it).  The mixed float/double
 // comparisons of the reference are kept: z-window and half extents in double.
 // out[(b, p, k)] is written 1 where inside and left untouched otherwise.
-#include "common.h"
-#include <math.h>
+// The box expansion and the test itself live in pib_test.h (shared with roiaware_pool3d.hip).
+#include "pib_test.h"
 
 namespace nesie {
 
 constexpr int PIB_BLOCK = 256;
 constexpr int PIB_TILE = 256;  // boxes per LDS tile
-
-struct PibBox {
-  float cx, cy, czm;       // centre, z already shifted to mid height
-  double hl, hw, hh;       // half length (box[4]), half width (box[3]), half height
-  float cosa, sina;
-};
 
 __global__ __launch_bounds__(PIB_BLOCK) void points_in_boxes_batch_kernel(
     int boxes_num, int pts_num, const float *__restrict__ boxes,
@@ -38,31 +32,42 @@ __global__ __launch_bounds__(PIB_BLOCK) void points_in_boxes_batch_kernel(
     const int tn = boxes_num - t0 < PIB_TILE ? boxes_num - t0 : PIB_TILE;
     __syncthreads();
     for (int k = threadIdx.x; k < tn; k += PIB_BLOCK) {
-      const float *bx = boxes + (size_t)(t0 + k) * 7;
-      const float w = bx[3], l = bx[4], h = bx[5], rz = bx[6];
-      PibBox q;
-      q.cx = bx[0]; q.cy = bx[1];
-      q.czm = (float)((double)bx[2] + (double)h / 2.0);  // cz += h / 2.0
-      q.hl = (double)l / 2.0; q.hw = (double)w / 2.0; q.hh = (double)h / 2.0;
-      const float rot_angle = (float)((double)rz + M_PI / 2);
-      q.cosa = (float)cos((double)rot_angle);
-      q.sina = (float)sin((double)rot_angle);
-      sb[k] = q;
+      sb[k] = pib_expand(boxes + (size_t)(t0 + k) * 7);
     }
     __syncthreads();
     if (live) {
       for (int k = 0; k < tn; ++k) {
-        const PibBox q = sb[k];
-        if ((double)fabsf(__fsub_rn(z, q.czm)) > q.hh) continue;
-        const float sx = __fsub_rn(x, q.cx), sy = __fsub_rn(y, q.cy);
-        const float lx = __fadd_rn(__fmul_rn(sx, q.cosa), __fmul_rn(sy, -q.sina));
-        const float ly = __fadd_rn(__fmul_rn(sx, q.sina), __fmul_rn(sy, q.cosa));
-        const bool in = ((double)lx > -q.hl) & ((double)lx < q.hl) &
-                        ((double)ly > -q.hw) & ((double)ly < q.hw);
-        if (in) o[t0 + k] = 1;
+        if (pib_inside(sb[k], x, y, z)) o[t0 + k] = 1;
       }
     }
   }
+}
+
+// points_in_boxes_gpu (points_in_boxes_cuda.cu:51-77): the loop above with an early exit; out[(b, p)]
+// = the index of the FIRST box that holds the point, else -1; written in full (also with no box).
+__global__ __launch_bounds__(PIB_BLOCK) void points_in_boxes_gpu_kernel(
+    int boxes_num, int pts_num, const float *__restrict__ boxes,
+    const float *__restrict__ pts, int *__restrict__ out) {
+  __shared__ PibBox sb[PIB_TILE];
+  const int bi = blockIdx.y;
+  const int p = blockIdx.x * PIB_BLOCK + threadIdx.x;
+  const bool live = p < pts_num;
+  boxes += (size_t)bi * boxes_num * 7;
+  const float *pt = pts + ((size_t)bi * pts_num + (live ? p : pts_num - 1)) * 3;
+  const float x = pt[0], y = pt[1], z = pt[2];
+  int first = -1;
+  for (int t0 = 0; t0 < boxes_num; t0 += PIB_TILE) {
+    const int tn = boxes_num - t0 < PIB_TILE ? boxes_num - t0 : PIB_TILE;
+    // (the barrier before sb is refilled; the workgroup leaves together once every point is settled)
+    if (__syncthreads_and(!live || first >= 0)) break;
+    for (int k = threadIdx.x; k < tn; k += PIB_BLOCK) sb[k] = pib_expand(boxes + (size_t)(t0 + k) * 7);
+    __syncthreads();
+    if (live && first < 0) {
+      for (int k = 0; k < tn; ++k)
+        if (pib_inside(sb[k], x, y, z)) { first = t0 + k; break; }
+    }
+  }
+  if (live) out[(size_t)bi * pts_num + p] = first;
 }
 
 
@@ -100,27 +105,15 @@ __global__ __launch_bounds__(PIB_BLOCK) void vote_targets_kernel(
     for (int k = threadIdx.x; k < tn; k += PIB_BLOCK) {
       const float *bx = boxes + (size_t)(t0 + k) * 7;
       // LiDAR-frame box: (y, -x, z, dy, dx, dz, yaw): w = bx[4] (depth dy), l = bx[3] (depth dx)
-      const float w = bx[4], l = bx[3], h = bx[5], rz = bx[6];
+      const float h = bx[5];
       VtBox v;
-      v.q.cx = bx[1]; v.q.cy = -bx[0];
-      v.q.czm = (float)((double)bx[2] + (double)h / 2.0);
-      v.q.hl = (double)l / 2.0; v.q.hw = (double)w / 2.0; v.q.hh = (double)h / 2.0;
-      const float rot_angle = (float)((double)rz + M_PI / 2);
-      v.q.cosa = (float)cos((double)rot_angle);
-      v.q.sina = (float)sin((double)rot_angle);
+      v.q = pib_expand(bx[1], -bx[0], bx[2], /*w=*/bx[4], /*l=*/bx[3], h, bx[6]);
       v.gx = bx[0]; v.gy = bx[1]; v.gz = __fadd_rn(bx[2], __fmul_rn(h, 0.5f));
       sb[k] = v;
     }
     __syncthreads();
     for (int k = 0; k < tn; ++k) {
-      const PibBox q = sb[k].q;
-      if ((double)fabsf(__fsub_rn(z, q.czm)) > q.hh) continue;
-      const float sx = __fsub_rn(x, q.cx), sy = __fsub_rn(y, q.cy);
-      const float lx = __fadd_rn(__fmul_rn(sx, q.cosa), __fmul_rn(sy, -q.sina));
-      const float ly = __fadd_rn(__fmul_rn(sx, q.sina), __fmul_rn(sy, q.cosa));
-      const bool in = ((double)lx > -q.hl) & ((double)lx < q.hl) &
-                      ((double)ly > -q.hw) & ((double)ly < q.hw);
-      if (in) {
+      if (pib_inside(sb[k].q, x, y, z)) {
         const float gx = sb[k].gx, gy = sb[k].gy, gz = sb[k].gz;
         if (cnt == 0) { c1x = gx; c1y = gy; c1z = gz; }
         if (cnt == 1) { c2x = gx; c2y = gy; c2z = gz; }
@@ -156,6 +149,18 @@ extern "C" int nesie_points_in_boxes_batch(int b, int boxes_num, int pts_num,
   hipLaunchKernelGGL(points_in_boxes_batch_kernel, dim3(cdiv(pts_num, PIB_BLOCK), b),
                      dim3(PIB_BLOCK), 0, (hipStream_t)stream, boxes_num, pts_num, boxes, pts,
                      out);
+  return check_launch(W);
+}
+
+extern "C" int nesie_points_in_boxes_gpu(int b, int boxes_num, int pts_num, const float *boxes,
+                                         const float *pts, int *out, void *stream) {
+  const char *W = "points_in_boxes_gpu";
+  NESIE_REQUIRE(b >= 0 && boxes_num >= 0 && pts_num >= 0, W);
+  if (b == 0 || pts_num == 0) return NESIE_OK;
+  NESIE_REQUIRE(pts && out && (boxes || boxes_num == 0), W);
+  NESIE_REQUIRE(b <= 65535, W);
+  hipLaunchKernelGGL(points_in_boxes_gpu_kernel, dim3(cdiv(pts_num, PIB_BLOCK), b),
+                     dim3(PIB_BLOCK), 0, (hipStream_t)stream, boxes_num, pts_num, boxes, pts, out);
   return check_launch(W);
 }
 

@@ -8,8 +8,7 @@
 // here one workgroup per scene sorts, builds the K x K suppression bit matrix in LDS and
 // walks it once.
 #include "bev_overlap.h"
-#include "common.h"
-#include <math.h>
+#include "pib_test.h"
 
 namespace nesie {
 
@@ -112,17 +111,15 @@ __global__ __launch_bounds__(256) void zero_i32_kernel(int n, int *__restrict__ 
 }
 
 // ---- points_in_boxes_count ------------------------------------------------------------
-// Same inside-test as points_in_boxes.hip (points_in_boxes_cuda.cu:24-49), LiDAR-frame boxes;
-// counts[b, t] = number of the scene's points inside box t.
+// The inside-test of points_in_boxes.hip (pib_test.h; points_in_boxes_cuda.cu:24-49), LiDAR-frame
+// boxes; counts[b, t] = number of the scene's points inside box t.
 constexpr int PIC_BLOCK = 256;
 constexpr int PIC_TILE = 256;
-
-struct PicBox { float cx, cy, czm; double hl, hw, hh; float cosa, sina; };
 
 __global__ __launch_bounds__(PIC_BLOCK) void points_in_boxes_count_kernel(
     int boxes_num, int pts_num, const float *__restrict__ boxes,
     const float *__restrict__ pts, int *__restrict__ counts) {
-  __shared__ PicBox sb[PIC_TILE];
+  __shared__ PibBox sb[PIC_TILE];
   __shared__ int cnt[PIC_TILE];
   const int bi = blockIdx.y;
   const int p = blockIdx.x * PIC_BLOCK + threadIdx.x;
@@ -134,29 +131,12 @@ __global__ __launch_bounds__(PIC_BLOCK) void points_in_boxes_count_kernel(
     const int tn = boxes_num - t0 < PIC_TILE ? boxes_num - t0 : PIC_TILE;
     __syncthreads();
     for (int k = threadIdx.x; k < tn; k += PIC_BLOCK) {
-      const float *bx = boxes + (size_t)(t0 + k) * 7;
-      const float w = bx[3], l = bx[4], h = bx[5], rz = bx[6];
-      PicBox q;
-      q.cx = bx[0]; q.cy = bx[1];
-      q.czm = (float)((double)bx[2] + (double)h / 2.0);
-      q.hl = (double)l / 2.0; q.hw = (double)w / 2.0; q.hh = (double)h / 2.0;
-      const float rot_angle = (float)((double)rz + M_PI / 2);
-      q.cosa = (float)cos((double)rot_angle);
-      q.sina = (float)sin((double)rot_angle);
-      sb[k] = q;
+      sb[k] = pib_expand(boxes + (size_t)(t0 + k) * 7);
       cnt[k] = 0;
     }
     __syncthreads();
     for (int k = 0; k < tn; ++k) {
-      const PicBox q = sb[k];
-      bool in = live && !((double)fabsf(__fsub_rn(z, q.czm)) > q.hh);
-      if (in) {
-        const float sx = __fsub_rn(x, q.cx), sy = __fsub_rn(y, q.cy);
-        const float lx = __fadd_rn(__fmul_rn(sx, q.cosa), __fmul_rn(sy, -q.sina));
-        const float ly = __fadd_rn(__fmul_rn(sx, q.sina), __fmul_rn(sy, q.cosa));
-        in = ((double)lx > -q.hl) & ((double)lx < q.hl) & ((double)ly > -q.hw) &
-             ((double)ly < q.hw);
-      }
+      const bool in = live && pib_inside(sb[k], x, y, z);
       const unsigned long long m = __ballot(in);
       if (m && (threadIdx.x & 63) == 0) atomicAdd(&cnt[k], __popcll(m));
     }

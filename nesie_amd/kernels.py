@@ -623,6 +623,65 @@ class HipKernels:
         assert tuple(out.shape) == (b, m, t)
         _launch("nesie_points_in_boxes_batch", boxes, b, t, m, boxes, pts, out)
 
+    def points_in_boxes_gpu(self, boxes, pts, box_idx_of_points):
+        """boxes (B,T,7) LiDAR frame, pts (B,M,3) -> box_idx_of_points (B,M) i32: the first box
+        that holds the point, else -1; written in full."""
+        _check(boxes, pts, box_idx_of_points); _f32(boxes, pts); _i32(box_idx_of_points)
+        b, t, seven = boxes.shape
+        assert seven == 7 and pts.shape[0] == b and pts.shape[2] == 3
+        m = pts.shape[1]
+        assert tuple(box_idx_of_points.shape) == (b, m)
+        _launch("nesie_points_in_boxes_gpu", boxes, b, t, m, boxes, pts, box_idx_of_points)
+
+    @staticmethod
+    def roiaware_pool3d_sizes(n, p, c, out_size, m):
+        """-> (elements of pts_idx_of_voxels, of pooled / argmax, of pts_voxel); raises on sizes
+        the kernels refuse (nesie_roiaware_pool3d_sizes)."""
+        out = (ctypes.c_longlong * 3)()
+        _lib.call("nesie_roiaware_pool3d_sizes", n, p, c, *out_size, m, ctypes.addressof(out))
+        return tuple(out)
+
+    def roiaware_pool3d_forward(self, rois, pts, pts_feature, argmax, pts_idx_of_voxels,
+                                pooled_features, pool_method, pts_voxel=None):
+        """rois (N,7), pts (P,3), pts_feature (P,C) -> argmax, pooled_features (N,ox,oy,oz,C),
+        pts_idx_of_voxels (N,ox,oy,oz,m) and, when given, the membership table pts_voxel (N,P)
+        i32 that ``roiaware_pool3d_backward`` gathers through; all written in full
+        (nesie_roiaware_pool3d_forward; pool_method 0 = max, 1 = avg)."""
+        _check(rois, pts, pts_feature, argmax, pts_idx_of_voxels, pooled_features)
+        _f32(rois, pts, pts_feature, pooled_features); _i32(argmax, pts_idx_of_voxels)
+        n, p, c = rois.shape[0], pts.shape[0], pts_feature.shape[1]
+        assert tuple(rois.shape) == (n, 7) and tuple(pts.shape) == (p, 3)
+        assert tuple(pts_feature.shape) == (p, c)
+        assert pts_idx_of_voxels.dim() == 5 and pts_idx_of_voxels.shape[0] == n
+        ox, oy, oz, m = (int(s) for s in pts_idx_of_voxels.shape[1:])
+        assert tuple(pooled_features.shape) == (n, ox, oy, oz, c)
+        assert tuple(argmax.shape) == (n, ox, oy, oz, c)
+        assert pool_method in (0, 1)
+        if pts_voxel is not None:
+            _check(pts_voxel); _i32(pts_voxel)
+            assert tuple(pts_voxel.shape) == (n, p)
+        _launch("nesie_roiaware_pool3d_forward", rois, n, p, c, m, ox, oy, oz, rois, pts,
+                pts_feature, argmax, pts_idx_of_voxels, pooled_features, pts_voxel,
+                int(pool_method))
+
+    def roiaware_pool3d_backward(self, pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in,
+                                 pool_method):
+        """grad_out (N,ox,oy,oz,C) -> grad_in (P,C), written in full: every element the sum of its
+        contributions in ascending (box, voxel) order (nesie_roiaware_pool3d_backward).  The one
+        backward of this op: no float atomics in either setting of ``DETERMINISTIC``."""
+        _check(pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in)
+        _f32(grad_out, grad_in); _i32(pts_idx_of_voxels, argmax, pts_voxel)
+        assert grad_out.dim() == 5 and pts_idx_of_voxels.dim() == 5 and pts_voxel.dim() == 2
+        n, ox, oy, oz, c = (int(s) for s in grad_out.shape)
+        m = int(pts_idx_of_voxels.shape[4])
+        p = int(pts_voxel.shape[1])
+        assert tuple(pts_idx_of_voxels.shape) == (n, ox, oy, oz, m)
+        assert tuple(argmax.shape) == (n, ox, oy, oz, c)
+        assert tuple(pts_voxel.shape) == (n, p) and tuple(grad_in.shape) == (p, c)
+        assert pool_method in (0, 1)
+        _launch("nesie_roiaware_pool3d_backward", grad_out, n, p, ox, oy, oz, c, m,
+                pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in, int(pool_method))
+
     def vote_targets(self, points, gt_boxes, gt_count):
         """points (B,N,C>=3), depth-frame gt_boxes (B,T,7), gt_count (B) int64 -> vote targets
         (B,N,9) and masks (B,N) int64 of get_targets_single, one launch."""
