@@ -17,7 +17,19 @@ re-derived with the same fused multiply-add the forward's operand load used).
 
 Same function as the module-by-module path (which stays the CPU checker's and serves shapes the
 kernels are not built for); differences are fp32 summation order and fma-vs-mul/add rounding.
+
+How the host side is laid out: the two chain functions (``SAStackFn``, ``Stack1dFn``) describe their
+layers once as ``_Layer`` records (``_chain_layout``: which of the function's tensors is a layer's
+weight, bias, scale, shift -- the same positions address the gradient slots and the returned
+gradients), store and fetch their state through ``_save_chain`` / ``_saved_chain``, and share ONE
+walk back through the layers (``_chain_backward``); what differs between them -- how the top of
+the chain is entered, SA1's rebuilt first activation, the coordinate rows of the input gradient,
+the zero bias gradient -- stays in the two ``backward``s.  A layer that leaves through a max over
+groups of positions is ``_pooled_layer`` everywhere.  Which launches each function issues, in
+which order and over which buffers is pinned without a GPU by tests/test_fused_mlp_trace_cpu.py.
 """
+
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -135,6 +147,137 @@ def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_
     return dz, dw, dgamma, dbeta
 
 
+def _take_slots(ctx, first_index, tensors):
+    """Gradient slots of ``tensors`` = the arguments of ``ctx``'s forward from ``first_index`` on (None
+    entries are passed over) -- only for those whose gradient a backward will be asked for."""
+    return [grad_slots.take(t) if ctx.needs_input_grad[first_index + j] else None for j, t in enumerate(tensors)]
+
+
+def _pool_group(G):
+    return 16 if G == 16 else 32
+
+
+def _pooled_layer(backend, src, w, ng, in_coef, group, y=None, stat_part=None, norm_coef=None, zstar=False):
+    """A layer whose output leaves as its maximum over groups of ``group`` positions: src (..., Cin, P),
+    w (ng, Cout, Cin) -> (pooled (..., Cout, P / group), arg-max uint8, raw extremum | None) of
+    W . relu(in_coef src), through relu(norm(.)) when ``norm_coef`` is given.  The layer launch
+    leaves partial extrema (the minima too under a norm: its scale may be negative), the finishing
+    launch the rest.  ``norm_coef()`` runs BETWEEN the two and returns the norm's folded
+    coefficients (training: the statistics in ``stat_part`` are finalised there).  ``y``: the dense
+    output as well; ``zstar``: return the raw extremum behind every pooled value.  Leading axes
+    (scene, net) are one batch axis to the kernels."""
+    *lead, cin, P = src.shape
+    src = src.flatten(0, -3)
+    cout = w.shape[1]
+    pg = _pool_group(group)
+    normed = norm_coef is not None
+
+    def buf(n, dtype=src.dtype, batch=src.shape[:1]):
+        return torch.empty(*batch, cout, n, dtype=dtype, device=src.device)
+    pool_out = (buf(P // pg), buf(P // pg) if normed else None,
+                buf(P // pg, torch.uint8), buf(P // pg, torch.uint8) if normed else None)
+    backend.pw_layer_forward(src, w, ng=ng, in_coef=in_coef, in_relu=True, y=y, stat_part=stat_part,
+                             pool_group=pg, pool_min=normed, pool_out=pool_out)
+    coef = norm_coef() if normed else None
+    pooled, argmax = buf(P // group, batch=lead), buf(P // group, torch.uint8, lead)
+    raw = buf(P // group, batch=lead) if zstar else None
+    backend.pw_pool_finish(ng, P, group, pg, pool_out, coef, normed, pooled.flatten(0, -3), argmax.flatten(0, -3),
+                           zstar=raw)
+    return pooled, argmax, raw
+
+
+# ---- a chain's layers: one record per layer, one walk back through them ------------------------------
+
+class Stack1dLayer:
+    """Static description of one layer: ``bias`` (the conv has one), ``bn`` = None or
+    (running_mean, running_var, momentum, eps) (-> conv, BatchNorm, ReLU)."""
+
+    def __init__(self, bias, bn):
+        self.bias, self.bn = bool(bias), bn
+
+
+# One layer of a chain function (SAStackFn, Stack1dFn).  ``iw, ib, ig, ibeta``: where its weight,
+# conv bias, norm scale and shift sit among the function's ``*tensors`` (None = the layer has none)
+# -- which is also where their gradients sit in what the backward returns behind its three leading
+# Nones, and their slots in ``ctx.slots``; ``bn`` = the norm's (running_mean, running_var, momentum,
+# eps) or None.  The positions are static and live on ``ctx``; ``w, b, gamma, beta`` are filled in by
+# ``_bind`` from the forward's arguments or from the saved tensors.
+_Layer = namedtuple('_Layer', 'bn iw ib ig ibeta w b gamma beta', defaults=(None,) * 4)
+
+
+def _chain_layout(layers):
+    """[Stack1dLayer] -> [_Layer] without tensors: per layer W, then the bias if the conv has one,
+    then gamma, beta if it has a norm."""
+    chain, pos = [], 0
+    for lay in layers:
+        ib = pos + 1 if lay.bias else None
+        ig = pos + 1 + lay.bias if lay.bn is not None else None
+        chain.append(_Layer(lay.bn, pos, ib, ig, None if ig is None else ig + 1))
+        pos += 1 + lay.bias + (0 if lay.bn is None else 2)
+    return chain
+
+
+def _bind(chain, tensors):
+    def at(i):
+        return None if i is None else tensors[i]
+    return [lay._replace(w=at(lay.iw), b=at(lay.ib), gamma=at(lay.ig), beta=at(lay.ibeta)) for lay in chain]
+
+
+def _save_chain(ctx, chain, head, ys, coefs, tensors):
+    """What a chain's backward needs: ``head`` (the input and whatever else the function keeps), per
+    layer the raw conv output and the folded norm coefficients (None where there is none), the
+    layers' tensors -- and the gradient slots of the tensors whose gradient a kernel (or a fill)
+    writes: weights, norm scales / shifts, and the identically-zero bias in front of a norm (a plain
+    conv's bias gradient is a reduction of its own: nothing to gain there)."""
+    plain_bias = {lay.ib for lay in chain if lay.bn is None}
+    ctx.slots = _take_slots(ctx, 3, [None if i in plain_bias else t for i, t in enumerate(tensors)])
+    ctx.chain, ctx.n_head = chain, len(head)
+    ctx.save_for_backward(*head, *ys, *coefs, *tensors)
+
+
+def _saved_chain(ctx):
+    """-> (head, ys, coefs, the layers bound to the saved tensors) as ``_save_chain`` stored them."""
+    sv, h, L = ctx.saved_tensors, ctx.n_head, len(ctx.chain)
+    return sv[:h], sv[h:h + L], sv[h + L:h + 2 * L], _bind(ctx.chain, sv[h + 2 * L:])
+
+
+def _transposed(w):
+    """The (ng, Cin, Cout) view of a layer's weight that the input-gradient product reads:
+    w (S, Cout, Cin) of a 1-D chain, or a conv weight (Cout, Cin, 1, 1)."""
+    return w.transpose(1, 2) if w.dim() == 3 else w.flatten(1).t().unsqueeze(0)
+
+
+def _chain_backward(backend, ctx, lays, x, ys, coefs, grads, top, dz, pending=None, ng=1, input_grad=None,
+                    bottom=0):
+    """The walk from layer ``top`` down through a chain: per layer the norm backward and the weight
+    gradient, then the input-gradient launch that also leaves the reduction of the next norm
+    backward.  It is entered with ``dz`` = the gradient of layer ``top``'s raw output, or with
+    ``pending`` = (da, part): the gradient of its ACTIVATION and the reduction partials of its norm
+    backward, not applied yet.  Parameter gradients go into ``grads`` at the layers' positions (written
+    into ``ctx.slots`` where there are any).  At layer 0 it returns ``input_grad(dz, layer)``; without
+    an ``input_grad`` nobody reads the first layer's dz and it may never be written.  ``bottom`` > 0:
+    the walk ends in front of layer ``bottom - 1`` and returns that layer's pending."""
+    need, slots = ctx.needs_input_grad[3:], ctx.slots
+    for l in range(top, bottom - 1, -1):
+        lay = lays[l]
+        src, src_coef = (x, None) if l == 0 else (ys[l - 1], coefs[l - 1])
+        if pending is not None:     # norm backward of this layer, with its weight gradient
+            dz, dw, grads[lay.ig], grads[lay.ibeta] = _norm_backward_wgrad(
+                backend, pending[0], ys[l], lay.gamma, coefs[l], pending[1], src, src_coef, need[lay.iw], ng=ng,
+                need_dz=l > 0 or input_grad is not None, slots=(slots[lay.iw], slots[lay.ig], slots[lay.ibeta]))
+            if dw is not None:
+                grads[lay.iw] = dw.view(lay.w.shape)
+        elif need[lay.iw]:
+            grads[lay.iw] = _wgrad(backend, dz, src, src_coef, ng=ng, slot=slots[lay.iw]).view(lay.w.shape)
+        if l == 0:
+            return None if input_grad is None else input_grad(dz, lay)
+        # gradient of the previous layer's activation (+ the reduction of its norm backward)
+        da = dz.new_empty(dz.shape[0], src.shape[1], dz.shape[2])
+        part = backend.pw_dgrad_bn_reduce(dz, _transposed(lay.w), src, src_coef, da, ng=ng)
+        pending = (da, part)
+    return pending
+
+
 class SAStackFn(Function):
     """x (B, C0, M, ns) -> max_ns relu(bn_L(conv_L(... relu(bn_1(conv_1(x)))))) (B, C_L, M).
     ``fixed_lead`` = number of leading input channels that are inputs of the step (grouped
@@ -147,23 +290,24 @@ class SAStackFn(Function):
         x = x.contiguous()
         B, c0, M, ns = x.shape
         P = M * ns
-        L = len(params) // 3
+        chain = _chain_layout([Stack1dLayer(False, bn) for bn in bufs])      # no bias, always a norm
+        lays = _bind(chain, params)
+        L = len(lays)
         x3 = x.view(B, c0, P)
         ys, coefs = [], []
-        coef = None
-        pool_group = 16 if ns == 16 else 32
-        pool_out = None
+        coef = k4_mom = None
         need = ctx.needs_input_grad
         k4_ok = getattr(backend, 'k4_supported', None)
+        # (need[3:9]: the parameters of the first two layers -- all of them or nothing at all)
         ctx.k4 = bool(SA1_K4 and L >= 3 and k4_ok is not None and not need[0]
                       and (all(need[3:9]) or not any(need))
-                      and k4_ok(c0, params[0].shape[0], params[3].shape[0], P))
-        w0c = params[0].reshape(params[0].shape[0], c0) if ctx.k4 else None
-        for l in range(L):
-            w, gamma, beta = params[3 * l:3 * l + 3]
-            rm, rv, momentum, eps = bufs[l]
-            cout, cin = w.shape[0], w.shape[1]
-            w2 = w.reshape(1, cout, cin)
+                      and k4_ok(c0, lays[0].w.shape[0], lays[1].w.shape[0], P))
+        w0c = lays[0].w.reshape(lays[0].w.shape[0], c0) if ctx.k4 else None
+        for l, lay in enumerate(lays):
+            gamma, beta = lay.gamma, lay.beta
+            rm, rv, momentum, eps = lay.bn
+            cout, cin = lay.w.shape[0], lay.w.shape[1]
+            w2 = lay.w.reshape(1, cout, cin)
             src = x3 if l == 0 else ys[-1]
             last = l == L - 1
             # the pooled last layer without its dense pre-pool tensor (csrc/pool_tail.hip): the forward
@@ -186,128 +330,99 @@ class SAStackFn(Function):
                 backend.mlp_stat_finalize(part, B * P, gamma, beta, rm, rv, momentum, eps, new_coef)
             else:
                 part = x.new_empty(1, backend.pw_stat_slots(B, 1, cin, cout, P), cout, 4)
+
+                def finalize():
+                    backend.pw_stats_finalize(part, gamma, beta, rm, rv, momentum, eps, new_coef)
+                    return new_coef
                 if last:
-                    g = P // pool_group
-                    pool_out = (x.new_empty(B, cout, g), x.new_empty(B, cout, g),
-                                torch.empty(B, cout, g, dtype=torch.uint8, device=x.device),
-                                torch.empty(B, cout, g, dtype=torch.uint8, device=x.device))
-                backend.pw_layer_forward(src, w2, in_coef=coef, in_relu=True, y=y, stat_part=part,
-                                         pool_group=pool_group if last else 0, pool_min=last,
-                                         pool_out=pool_out)
-                backend.pw_stats_finalize(part, gamma, beta, rm, rv, momentum, eps, new_coef)
+                    pooled, argmax, raw = _pooled_layer(backend, src, w2, 1, coef, ns, y=y, stat_part=part,
+                                                        norm_coef=finalize, zstar=tail)
+                    if tail:
+                        y = raw             # the raw extremum behind every pooled value
+                else:
+                    backend.pw_layer_forward(src, w2, in_coef=coef, in_relu=True, y=y, stat_part=part)
+                    finalize()
             coef = new_coef
             ys.append(y)
             coefs.append(coef)
-        cl = params[3 * (L - 1)].shape[0]
-        pooled = x.new_empty(B, cl, M)
-        argmax = torch.empty(B, cl, M, dtype=torch.uint8, device=x.device)
-        ctx.tail = ys[-1] is None
-        if ctx.tail:
-            ys[-1] = x.new_empty(B, cl, M)            # the raw extremum behind every pooled value
-        backend.pw_pool_finish(1, P, ns, pool_group, pool_out, coef, True, pooled, argmax,
-                               zstar=ys[-1] if ctx.tail else None)
-        ctx.L, ctx.ns, ctx.fixed_lead = L, ns, int(fixed_lead)
-        # gradient slots of (weight, gamma, beta) per layer -- only when a backward will follow
-        ctx.slots = [grad_slots.take(t) if ctx.needs_input_grad[3 + j] else None for j, t in enumerate(params)]
-        ctx.save_for_backward(x3, pooled, argmax, *ys, *coefs, *params, *([k4_mom] if ctx.k4 else []))
+        ctx.tail = tail
+        ctx.ns, ctx.fixed_lead = ns, int(fixed_lead)
+        _save_chain(ctx, chain, (x3, pooled, argmax, k4_mom), ys, coefs, params)
         ctx.mark_non_differentiable(argmax)
         return pooled
 
     @staticmethod
     def backward(ctx, g):
-        L, ns = ctx.L, ctx.ns
-        sv = ctx.saved_tensors
-        x3, pooled, argmax = sv[:3]
-        ys, coefs = sv[3:3 + L], sv[3 + L:3 + 2 * L]
-        params = sv[3 + 2 * L:3 + 5 * L]
+        (x3, pooled, argmax, k4_mom), ys, coefs, lays = _saved_chain(ctx)
+        ns, slots, need = ctx.ns, ctx.slots, ctx.needs_input_grad
         backend = backend_for(g)
         B, c0, P = x3.shape
         M = P // ns
-        grads = [None] * (3 * L)
-        yl = ys[-1]
+        grads = [None] * len(slots)
+        last, yl = lays[-1], ys[-1]
         cl = yl.shape[1]
-        slots = ctx.slots
-        dgamma, dbeta = _dst(slots[3 * (L - 1) + 1], g, cl), _dst(slots[3 * (L - 1) + 2], g, cl)
-        grads[3 * (L - 1) + 1], grads[3 * (L - 1) + 2] = dgamma, dbeta
-        dx = None
-        pending = None          # (da, part) of the layer whose norm backward has not been applied yet
-        top = L - 1
+        dgamma, dbeta = _dst(slots[last.ig], g, cl), _dst(slots[last.ibeta], g, cl)
+        grads[last.ig], grads[last.ibeta] = dgamma, dbeta
+        dy = pending = None
+        top = len(lays) - 1
         if ctx.tail:
             # last layer without its dense tensors: yl is the raw extremum per (channel, group)
-            wl = params[3 * (L - 1)]
-            need_w = ctx.needs_input_grad[3 + 3 * (L - 1)]
-            dwl = _dst(slots[3 * (L - 1)], g, cl, wl.shape[1]) if need_w else None
-            pending = backend.pool_tail_backward(g.contiguous(), pooled, yl, argmax, coefs[-1],
-                                                 params[3 * (L - 1) + 1], wl.reshape(cl, wl.shape[1]),
-                                                 ys[L - 2], coefs[L - 2], ns, dgamma, dbeta, dw=dwl)
+            wl = last.w
+            need_w = need[3 + last.iw]
+            dwl = _dst(slots[last.iw], g, cl, wl.shape[1]) if need_w else None
+            pending = backend.pool_tail_backward(g.contiguous(), pooled, yl, argmax, coefs[-1], last.gamma,
+                                                 wl.reshape(cl, wl.shape[1]), ys[-2], coefs[-2], ns,
+                                                 dgamma, dbeta, dw=dwl)
             if need_w:
-                grads[3 * (L - 1)] = dwl.view_as(wl)
-            top = L - 2
+                grads[last.iw] = dwl.view_as(wl)
+            top -= 1
         else:
             # last layer: BatchNorm + ReLU + max backward into the dense raw-output gradient
             dy = torch.empty_like(yl)
-            backend.bn_relu_maxpool_backward(g.contiguous(), argmax, yl.view(B, cl, M, ns), pooled,
-                                             params[3 * (L - 1) + 1], None, coefs[-1],
-                                             dy.view(B, cl, M, ns), dgamma, dbeta)
-        for l in range(top, -1, -1):
-            w = params[3 * l]
-            cout, cin = w.shape[0], w.shape[1]
-            w2 = w.reshape(cout, cin)
-            src = x3 if l == 0 else ys[l - 1]
-            src_coef = None if l == 0 else coefs[l - 1]
-            need_w = ctx.needs_input_grad[3 + 3 * l]
-            if ctx.k4 and l == 1:
-                # second layer over the rebuilt first activation: its fused norm backward + weight
-                # gradient and ONLY the reductions of its input gradient -- they determine the
-                # first layer's norm backward and weight gradient (nesie_k4_first_layer_wgrad) --
-                # as one launch: the layer's dZ never leaves the chip
-                assert pending is not None
-                w0 = params[0]
-                w0c = w0.reshape(w0.shape[0], c0)
-                dgamma, dbeta = _dst(slots[4], g, cout), _dst(slots[5], g, cout)
-                dw = _dst(slots[3], g, 1, cout, cin)
-                part, g_part = backend.pw_wgrad_bn_backward_k4_fused(
-                    pending[0], ys[1], coefs[1], params[4], pending[1], x3, w0c, coefs[0], w2, dw, dgamma, dbeta,
-                    final=slots[3] is not None)
-                grads[3], grads[4], grads[5] = dw.view_as(w), dgamma, dbeta
-                dgamma0, dbeta0 = _dst(slots[1], g, cin), _dst(slots[2], g, cin)
-                bnb = backend.pw_bnb_coef(part, coefs[0], params[1], float(B) * float(P), dgamma0, dbeta0)
-                dw0 = _dst(slots[0], g, cin, c0)
-                backend.k4_first_layer_wgrad(sv[3 + 5 * L], w0c, bnb, g_part, dw0)
-                grads[0], grads[1], grads[2] = dw0.view_as(w0), dgamma0, dbeta0
-                break
-            if pending is not None:     # norm backward of this layer, with its weight gradient
-                dy, dw, dgamma, dbeta = _norm_backward_wgrad(
-                    backend, pending[0], ys[l], params[3 * l + 1], coefs[l], pending[1], src, src_coef,
-                    need_w, need_dz=l > 0 or bool(ctx.needs_input_grad[0]), slots=slots[3 * l:3 * l + 3])
-                grads[3 * l + 1], grads[3 * l + 2] = dgamma, dbeta
-                if dw is not None:
-                    grads[3 * l] = dw.view_as(w)
-            elif need_w:
-                grads[3 * l] = _wgrad(backend, dy, src, src_coef, slot=slots[3 * l]).view_as(w)
-            if l == 0:
-                if ctx.needs_input_grad[0]:
-                    # the layer kernel serves up to 256 output rows: the (at most 3) coordinate
-                    # rows in front are a separate skinny product, or zero when nobody reads them
-                    lead = 3 if c0 in (131, 259) else 0
-                    dx = dy.new_empty(B, c0, P)
-                    if backend.pw_supported(cout, c0 - lead, P):
-                        backend.pw_layer_forward(dy, w2[:, lead:].t().unsqueeze(0), y=dx[:, lead:])
-                        if lead and ctx.fixed_lead >= lead:
-                            dx[:, :lead].zero_()
-                        elif lead:
-                            torch.bmm(w2[:, :lead].t().unsqueeze(0).expand(B, -1, -1), dy,
-                                      out=dx[:, :lead])
-                    else:
-                        dx = torch.bmm(w2.t().unsqueeze(0).expand(B, -1, -1), dy)
-                break
-            # gradient of the previous layer's activation (+ the reduction of its norm backward)
-            da = dy.new_empty(B, cin, P)
-            part = backend.pw_dgrad_bn_reduce(dy, w2.t().unsqueeze(0), ys[l - 1], coefs[l - 1], da)
-            pending = (da, part)
-        if dx is not None:
-            dx = dx.view(B, c0, M, ns)
-        return (dx, None, None) + tuple(grads)
+            backend.bn_relu_maxpool_backward(g.contiguous(), argmax, yl.view(B, cl, M, ns), pooled, last.gamma,
+                                             None, coefs[-1], dy.view(B, cl, M, ns), dgamma, dbeta)
+
+        def input_grad(dy, lay):
+            # the layer kernel serves up to 256 output rows: the (at most 3) coordinate
+            # rows in front are a separate skinny product, or zero when nobody reads them
+            cout = lay.w.shape[0]
+            w2 = lay.w.reshape(cout, c0)
+            lead = 3 if c0 in (131, 259) else 0
+            dx = dy.new_empty(B, c0, P)
+            if backend.pw_supported(cout, c0 - lead, P):
+                backend.pw_layer_forward(dy, w2[:, lead:].t().unsqueeze(0), y=dx[:, lead:])
+                if lead and ctx.fixed_lead >= lead:
+                    dx[:, :lead].zero_()
+                elif lead:
+                    torch.bmm(w2[:, :lead].t().unsqueeze(0).expand(B, -1, -1), dy,
+                              out=dx[:, :lead])
+            else:
+                dx = torch.bmm(w2.t().unsqueeze(0).expand(B, -1, -1), dy)
+            return dx.view(B, c0, M, ns)
+        out = _chain_backward(backend, ctx, lays, x3, ys, coefs, grads, top, dy, pending,
+                              input_grad=input_grad if need[0] else None, bottom=2 if ctx.k4 else 0)
+        if not ctx.k4:
+            return (out, None, None) + tuple(grads)
+        # second layer over the rebuilt first activation: its fused norm backward + weight
+        # gradient and ONLY the reductions of its input gradient -- they determine the
+        # first layer's norm backward and weight gradient (nesie_k4_first_layer_wgrad) --
+        # as one launch: the layer's dZ never leaves the chip
+        da, part = out
+        first, second = lays[:2]
+        cout, cin = second.w.shape[0], second.w.shape[1]
+        w0c = first.w.reshape(first.w.shape[0], c0)
+        dgamma, dbeta = _dst(slots[second.ig], g, cout), _dst(slots[second.ibeta], g, cout)
+        dw = _dst(slots[second.iw], g, 1, cout, cin)
+        part, g_part = backend.pw_wgrad_bn_backward_k4_fused(
+            da, ys[1], coefs[1], second.gamma, part, x3, w0c, coefs[0], second.w.reshape(cout, cin), dw,
+            dgamma, dbeta, final=slots[second.iw] is not None)
+        grads[second.iw], grads[second.ig], grads[second.ibeta] = dw.view_as(second.w), dgamma, dbeta
+        dgamma0, dbeta0 = _dst(slots[first.ig], g, cin), _dst(slots[first.ibeta], g, cin)
+        bnb = backend.pw_bnb_coef(part, coefs[0], first.gamma, float(B) * float(P), dgamma0, dbeta0)
+        dw0 = _dst(slots[first.iw], g, cin, c0)
+        backend.k4_first_layer_wgrad(k4_mom, w0c, bnb, g_part, dw0)
+        grads[first.iw], grads[first.ig], grads[first.ibeta] = dw0.view_as(first.w), dgamma0, dbeta0
+        return (None, None, None) + tuple(grads)
 
 
 def _pooled_tail_whole(cin, cout):
@@ -318,10 +433,28 @@ def _pooled_tail_whole(cin, cout):
     return cout % 128 == 0 or (cout == 64 and cin <= 128)
 
 
+def _native_norm(norm, training, only_2d=False):
+    """True for the native norm layer with its ReLU folded in, in the asked mode: training = batch
+    statistics, an affine transform and running statistics to update; evaluation = running
+    statistics to apply."""
+    from .norm import FusedBNReLU1d, FusedBNReLU2d
+    if not (isinstance(norm, FusedBNReLU2d if only_2d else (FusedBNReLU1d, FusedBNReLU2d))
+            and norm.fuse_relu and norm.track_running_stats):
+        return False
+    if training:
+        return bool(norm.training and norm.affine and norm.momentum is not None)
+    return not norm.training and norm.running_mean is not None
+
+
+def _sa_layer_ok(layer, cin, training):
+    """A bias-free 1x1 conv from ``cin`` channels with a native 2-D norm + ReLU behind it."""
+    return (_native_norm(getattr(layer, 'norm', None), training, only_2d=True) and layer.act_fused
+            and layer.conv.bias is None and layer.conv.in_channels == cin)
+
+
 def sa_stack_supported(backend, x, layers):
     """True when ``SAStackFn`` serves this shared MLP: native training BatchNorm behind bias-free
     1x1 convs, fp32, nsample in {16, 32, 64}, every layer inside the built tiles."""
-    from .norm import FusedBNReLU2d
     if not ENABLED or backend.name != 'hip' or x.dtype != torch.float32 or x.dim() != 4 \
             or len(layers) < 2:
         return False
@@ -331,14 +464,9 @@ def sa_stack_supported(backend, x, layers):
     P = M * ns
     cin = c0
     for i, layer in enumerate(layers):
-        norm = getattr(layer, 'norm', None)
-        if not (isinstance(norm, FusedBNReLU2d) and layer.act_fused and layer.conv.bias is None
-                and norm.training and norm.affine and norm.track_running_stats
-                and norm.momentum is not None):
+        if not _sa_layer_ok(layer, cin, training=True):
             return False
         cout = layer.conv.out_channels
-        if layer.conv.in_channels != cin:
-            return False
         first_stream = i == 0 and cin <= 8 and len(layers) > 1
         if not first_stream and not backend.pw_supported(cin, cout, P):
             return False
@@ -353,7 +481,6 @@ def sa_stack_supported(backend, x, layers):
 def sa_stack_eval_supported(backend, x, layers):
     """True when ``sa_stack_eval`` serves this shared MLP: evaluation-mode norms with running
     statistics, no autograd, shapes inside the built tiles."""
-    from .norm import FusedBNReLU2d
     if not ENABLED or backend.name != 'hip' or x.dtype != torch.float32 or x.dim() != 4 \
             or len(layers) < 2 or torch.is_grad_enabled():
         return False
@@ -361,10 +488,7 @@ def sa_stack_eval_supported(backend, x, layers):
     if ns not in (16, 32, 64):
         return False
     for layer in layers:
-        norm = getattr(layer, 'norm', None)
-        if not (isinstance(norm, FusedBNReLU2d) and layer.act_fused and layer.conv.bias is None
-                and not norm.training and norm.track_running_stats and norm.running_mean is not None
-                and layer.conv.in_channels == cin
+        if not (_sa_layer_ok(layer, cin, training=False)
                 and backend.pw_supported(cin, layer.conv.out_channels, M * ns)):
             return False
         if layer is layers[-1] and not _pooled_tail_whole(cin, layer.conv.out_channels):
@@ -382,27 +506,16 @@ def sa_stack_eval(x, layers):
     B, c0, M, ns = x.shape
     P = M * ns
     src, coef = x.view(B, c0, P), None
-    pool_group = 16 if ns == 16 else 32
-    pool_out = None
-    for i, layer in enumerate(layers):
+    for layer in layers[:-1]:
         cout, cin = layer.conv.out_channels, layer.conv.in_channels
-        w2 = layer.conv.weight.reshape(1, cout, cin)
         y = x.new_empty(B, cout, P)
-        if i == len(layers) - 1:
-            g = P // pool_group
-            pool_out = (x.new_empty(B, cout, g), x.new_empty(B, cout, g),
-                        torch.empty(B, cout, g, dtype=torch.uint8, device=x.device),
-                        torch.empty(B, cout, g, dtype=torch.uint8, device=x.device))
-            part = x.new_empty(1, backend.pw_stat_slots(B, 1, cin, cout, P), cout, 4)
-            backend.pw_layer_forward(src, w2, in_coef=coef, in_relu=True, y=y, stat_part=part,
-                                     pool_group=pool_group, pool_min=True, pool_out=pool_out)
-        else:
-            backend.pw_layer_forward(src, w2, in_coef=coef, in_relu=True, y=y)
+        backend.pw_layer_forward(src, layer.conv.weight.reshape(1, cout, cin), in_coef=coef, in_relu=True, y=y)
         src, coef = y, layer.norm.eval_coef()
-    pooled = x.new_empty(B, src.shape[1], M)
-    argmax = torch.empty(B, src.shape[1], M, dtype=torch.uint8, device=x.device)
-    backend.pw_pool_finish(1, P, ns, pool_group, pool_out, coef, True, pooled, argmax)
-    return pooled
+    layer = layers[-1]
+    cout, cin = layer.conv.out_channels, layer.conv.in_channels
+    part = x.new_empty(1, backend.pw_stat_slots(B, 1, cin, cout, P), cout, 4)
+    return _pooled_layer(backend, src, layer.conv.weight.reshape(1, cout, cin), 1, coef, ns,
+                         y=x.new_empty(B, cout, P), stat_part=part, norm_coef=layer.norm.eval_coef)[0]
 
 
 def sa_stack(x, layers, fixed_lead=0):
@@ -484,27 +597,13 @@ def stack_groups(groups):
 #   MiniHeadFn : c0 -> (f without its bias, max_G of it)
 #   MiniTailFn : (f, small) -> max_G conv4(relu(bn1(W_l f + small)))
 
-def _pool_group(G):
-    return 16 if G == 16 else 32
-
-
 def mini_head_kernels(backend, c0, coef0, w3, G):
     """c0 (B,S,H0,P) raw, coef0 (S*H0,4) -> c = W3 . relu(coef0 c0) (B,S,half,P), its max over
     groups of G positions g (B,S,half,P/G) and the arg-max."""
     B, S, H0, P = c0.shape
     half = w3.shape[1]
-    pg = _pool_group(G)
     c = c0.new_empty(B, S, half, P)
-    npg = P // pg
-    pool_out = (c0.new_empty(B * S, half, npg), None,
-                torch.empty(B * S, half, npg, dtype=torch.uint8, device=c0.device), None)
-    backend.pw_layer_forward(c0.view(B * S, H0, P), w3, ng=S, in_coef=coef0, in_relu=True,
-                             y=c.view(B * S, half, P), pool_group=pg, pool_min=False,
-                             pool_out=pool_out)
-    g = c0.new_empty(B, S, half, P // G)
-    arg = torch.empty(B, S, half, P // G, dtype=torch.uint8, device=c0.device)
-    backend.pw_pool_finish(S, P, G, pg, pool_out, None, False, g.view(B * S, half, -1),
-                           arg.view(B * S, half, -1))
+    g, arg, _ = _pooled_layer(backend, c0, w3, S, coef0, G, y=c.view(B * S, half, P))
     return c, g, arg
 
 
@@ -521,19 +620,7 @@ def mini_tail_first(backend, c, small, wl, G):
 
 def mini_tail_second(backend, y, coef1, w4, G):
     """max over groups of G positions of W4 . relu(coef1 y) -> (B,S,F,P/G) and the arg-max."""
-    B, S, H2, P = y.shape
-    F = w4.shape[1]
-    pg = _pool_group(G)
-    npg = P // pg
-    pool_out = (y.new_empty(B * S, F, npg), None,
-                torch.empty(B * S, F, npg, dtype=torch.uint8, device=y.device), None)
-    backend.pw_layer_forward(y.view(B * S, H2, P), w4, ng=S, in_coef=coef1, in_relu=True,
-                             pool_group=pg, pool_min=False, pool_out=pool_out)
-    out = y.new_empty(B, S, F, P // G)
-    arg = torch.empty(B, S, F, P // G, dtype=torch.uint8, device=y.device)
-    backend.pw_pool_finish(S, P, G, pg, pool_out, None, False, out.view(B * S, F, -1),
-                           arg.view(B * S, F, -1))
-    return out, arg
+    return _pooled_layer(backend, y, w4, y.shape[1], coef1, G)[:2]
 
 
 def _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3):
@@ -578,6 +665,16 @@ def _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, G, need_w3,
     return da0, part, dw3
 
 
+def _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta):
+    """The first norm's backward as its own apply pass: (da0, part) of ``_mini_head_backward`` -> the
+    gradient of c0; writes dgamma, dbeta."""
+    B, S, H0, P = c0.shape
+    dc0 = torch.empty_like(c0)
+    backend.bn_relu_backward_apply(da0.view(B, S * H0, P), c0.view(B, S * H0, P), gamma0, None, coef0, part,
+                                   dc0.view(B, S * H0, P), dgamma, dbeta)
+    return dc0
+
+
 class MiniHeadFn(Function):
     """c0 (B, S, H0, K*G) raw first-conv outputs of S stacked nets (+ their (sum, sum^2)
     partials) -> c = W3 . relu(bn0(c0)) (B, S, half, K*G) and g = max_G c (B, S, half, K)."""
@@ -588,8 +685,7 @@ class MiniHeadFn(Function):
         c0 = c0.contiguous()
         c, g, arg, coef0 = _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3)
         ctx.G = G
-        ctx.slots = [grad_slots.take(t) if ctx.needs_input_grad[4 + j] else None
-                     for j, t in enumerate((gamma0, beta0, w3))]
+        ctx.slots = _take_slots(ctx, 4, (gamma0, beta0, w3))
         ctx.save_for_backward(c0, coef0, arg, gamma0, beta0, w3)
         ctx.mark_non_differentiable(arg)
         return c, g
@@ -602,9 +698,7 @@ class MiniHeadFn(Function):
         da0, part, dw3 = _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, ctx.G,
                                              ctx.needs_input_grad[6], ctx.slots[2])
         dgamma, dbeta = _dst(ctx.slots[0], c0, S * H0), _dst(ctx.slots[1], c0, S * H0)
-        dc0 = torch.empty_like(c0)
-        backend.bn_relu_backward_apply(da0.view(B, S * H0, P), c0.view(B, S * H0, P), gamma0,
-                                       None, coef0, part, dc0.view(B, S * H0, P), dgamma, dbeta)
+        dc0 = _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta)
         return dc0, None, None, None, dgamma, dbeta, dw3
 
 
@@ -633,8 +727,7 @@ class BlendMiniHeadFn(Function):
                                    stat_partial=c0_part)
         c, g, arg, coef0 = _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3)
         ctx.G, ctx.dims = G, (segs, seg_len, b, m, pitch, h)
-        ctx.slots = [grad_slots.take(t) if ctx.needs_input_grad[9 + j] else None
-                     for j, t in enumerate((gamma0, beta0, w3))]
+        ctx.slots = _take_slots(ctx, 9, (gamma0, beta0, w3))
         ctx.save_for_backward(c0, coef0, arg, gamma0, w3, idx, weight, rel)
         ctx.mark_non_differentiable(arg)
         return c, g
@@ -656,9 +749,7 @@ class BlendMiniHeadFn(Function):
             backend.blend_conv_backward(da0.view(B, S, H0, P), h, idx, weight, rel, d_table, d_wx,
                                         segs, seg_len, bn_z=c0, bnb=bnb)
         else:       # A/B switch: the separate apply pass
-            dc0 = torch.empty_like(c0)
-            backend.bn_relu_backward_apply(da0.view(B, S * H0, P), c0.view(B, S * H0, P), gamma0,
-                                           None, coef0, part, dc0.view(B, S * H0, P), dgamma, dbeta)
+            dc0 = _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta)
             backend.blend_conv_backward(dc0, h, idx, weight, rel, d_table, d_wx, segs, seg_len)
         return d_table, d_wx, None, None, None, None, None, None, None, dgamma, dbeta, dw3
 
@@ -686,8 +777,7 @@ class MiniTailFn(Function):
         backend.pw_stats_finalize(part, gamma1, beta1, rm, rv, momentum, eps, coef1)
         out, arg = mini_tail_second(backend, y, coef1, w4, G)
         ctx.G = G
-        ctx.slots = [grad_slots.take(t) if ctx.needs_input_grad[5 + j] else None
-                     for j, t in enumerate((gamma1, beta1, w4))]
+        ctx.slots = _take_slots(ctx, 5, (gamma1, beta1, w4))
         ctx.save_for_backward(c, y, coef1, arg, wl, gamma1, beta1, w4)
         ctx.mark_non_differentiable(arg)
         return out
@@ -835,14 +925,6 @@ class AddChannelBias(Function):
         return g, db
 
 
-class Stack1dLayer:
-    """Static description of one layer: ``bias`` (the conv has one), ``bn`` = None or
-    (running_mean, running_var, momentum, eps) (-> conv, BatchNorm, ReLU)."""
-
-    def __init__(self, bias, bn):
-        self.bias, self.bn = bool(bias), bn
-
-
 class Stack1dFn(Function):
     """x (NB, C0, P), batch n uses weight group n % S.  Layers l = 0 .. L-1:
     y_l = W_l . a_{l-1} (+ bias_l), a_l = relu(bn_l(y_l)) for a layer with a norm, a_l = y_l
@@ -860,20 +942,11 @@ class Stack1dFn(Function):
         backend = backend_for(x)
         x = x.contiguous()
         NB, c0, P = x.shape
-        ts = list(tensors)
-        per_layer, pos = [], 0
-        for lay in layers:
-            w = ts[pos]; pos += 1
-            b = None
-            if lay.bias:
-                b = ts[pos]; pos += 1
-            gamma = beta = None
-            if lay.bn is not None:
-                gamma, beta = ts[pos], ts[pos + 1]; pos += 2
-            per_layer.append((w, b, gamma, beta))
+        chain = _chain_layout(layers)
         src, coef = x, None
         ys, coefs = [], []
-        for lay, (w, b, gamma, beta) in zip(layers, per_layer):
+        for lay in _bind(chain, tensors):
+            w, b = lay.w, None if lay.b is None else lay.b.detach().contiguous()
             cout = w.shape[1]
             y = x.new_empty(NB, cout, P)
             if lay.bn is not None:
@@ -881,135 +954,70 @@ class Stack1dFn(Function):
                 part = x.new_empty(S, backend.pw_stat_slots(NB, S, w.shape[2], cout, P), cout, 4)
                 backend.pw_layer_forward(src, w, ng=S, in_coef=coef, in_relu=True, y=y, stat_part=part)
                 coef = x.new_empty(S * cout, 4)
-                backend.pw_stats_finalize(part, gamma, beta, rm, rv, momentum, eps, coef,
-                                          chan_bias=None if b is None else b.detach().contiguous())
+                backend.pw_stats_finalize(part, lay.gamma, lay.beta, rm, rv, momentum, eps, coef, chan_bias=b)
             else:
-                backend.pw_layer_forward(src, w, ng=S, in_coef=coef, in_relu=True, y=y,
-                                         bias=None if b is None else b.detach().contiguous())
+                backend.pw_layer_forward(src, w, ng=S, in_coef=coef, in_relu=True, y=y, bias=b)
                 coef = None
             ys.append(y)
             coefs.append(coef)
             src = y
         out = ys[-1]
-        if layers[-1].bn is not None:      # the last activation is somebody's input: materialise it
+        if chain[-1].bn is not None:      # the last activation is somebody's input: materialise it
             cl = out.shape[1]
             act = torch.empty_like(out)
             backend.affine_relu_forward(out.view(NB // S, S * cl, P), coefs[-1], True,
                                         act.view(NB // S, S * cl, P))
             out = act
-        ctx.layers, ctx.S, ctx.n_tensors = layers, S, len(tensors)
-        # gradient slots of the tensors whose gradient a kernel (or a fill) writes: weights, norm
-        # scales / shifts, and the identically-zero bias in front of a norm (a plain conv's bias
-        # gradient is an ATen reduction: nothing to gain there)
-        ctx.slots, pos = [None] * len(tensors), 0
-        take = lambda i: grad_slots.take(ts[i]) if ctx.needs_input_grad[3 + i] else None  # noqa: E731
-        for lay in layers:
-            ctx.slots[pos] = take(pos); pos += 1
-            if lay.bias:
-                if lay.bn is not None:
-                    ctx.slots[pos] = take(pos)
-                pos += 1
-            if lay.bn is not None:
-                ctx.slots[pos], ctx.slots[pos + 1] = take(pos), take(pos + 1)
-                pos += 2
-        ctx.save_for_backward(x, *ys, *[c for c in coefs if c is not None], *tensors)
+        ctx.S = S
+        _save_chain(ctx, chain, (x,), ys, coefs, tensors)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        layers, S = ctx.layers, ctx.S
-        L = len(layers)
-        sv = list(ctx.saved_tensors)
-        x, ys = sv[0], sv[1:1 + L]
-        ncoef = sum(1 for lay in layers if lay.bn is not None)
-        coef_list = sv[1 + L:1 + L + ncoef]
-        ts = sv[1 + L + ncoef:]
-        coefs, ci_ = [], 0
-        for lay in layers:
-            if lay.bn is not None:
-                coefs.append(coef_list[ci_]); ci_ += 1
-            else:
-                coefs.append(None)
-        per_layer, pos, slots = [], 0, []
-        for lay in layers:
-            sl = {'w': pos}
-            w = ts[pos]; pos += 1
-            b = gamma = beta = None
-            if lay.bias:
-                sl['b'] = pos; b = ts[pos]; pos += 1
-            if lay.bn is not None:
-                sl['g'] = pos; gamma, beta = ts[pos], ts[pos + 1]; pos += 2
-            per_layer.append((w, b, gamma, beta))
-            slots.append(sl)
+        (x,), ys, coefs, lays = _saved_chain(ctx)
+        S, slots, need = ctx.S, ctx.slots, ctx.needs_input_grad
         backend = backend_for(dout)
         NB, c0, P = x.shape
         B = NB // S
-        grads = [None] * ctx.n_tensors
-        need = ctx.needs_input_grad
-        tslots = ctx.slots
-
-        def zero_bias(l):      # the bias in front of layer l's norm: gradient identically zero
-            # With a slot in the flat gradient vector the answer is None: FlatTrainState.collect()
-            # zero-fills every parameter that got no gradient (one multi-tensor fill for all of
-            # them), so whatever an earlier step, another path or a loaded vector left in the slot
-            # is overwritten in every step.  Without a flat state: a zero tensor, as ATen returns
-            # (a None would make a per-parameter optimiser skip the parameter).
-            sl = tslots[slots[l]['b']]
-            return None if sl is not None else torch.zeros_like(per_layer[l][1])
+        grads = [None] * len(slots)
+        last = lays[-1]
         # a channel slice of a wider gradient (the outputs of several chains concatenated by their
         # consumer) is batch-strided: the layer kernels take a batch stride, no copy needed
-        if not (S == 1 and layers[-1].bn is None and dout.stride(2) == 1 and dout.stride(1) == P):
+        if not (S == 1 and last.bn is None and dout.stride(2) == 1 and dout.stride(1) == P):
             dout = dout.contiguous()
         # gradient of the last layer's RAW output
-        w, b, gamma, beta = per_layer[-1]
         cl = ys[-1].shape[1]
-        if layers[-1].bn is not None:
-            coef = coefs[-1]
+        if last.bn is not None:
             dz = torch.empty_like(ys[-1])
-            dgamma = _dst(tslots[slots[-1]['g']], dout, S * cl)
-            dbeta = _dst(tslots[slots[-1]['g'] + 1], dout, S * cl)
-            backend.bn_relu_backward(dout.view(B, S * cl, P), ys[-1].view(B, S * cl, P), None, gamma, beta,
-                                     None, None, coef, True, dz.view(B, S * cl, P), dgamma, dbeta)
-            grads[slots[-1]['g']], grads[slots[-1]['g'] + 1] = dgamma, dbeta
-            if 'b' in slots[-1] and need[3 + slots[-1]['b']]:
-                grads[slots[-1]['b']] = zero_bias(L - 1)
+            dgamma, dbeta = _dst(slots[last.ig], dout, S * cl), _dst(slots[last.ibeta], dout, S * cl)
+            backend.bn_relu_backward(dout.view(B, S * cl, P), ys[-1].view(B, S * cl, P), None, last.gamma,
+                                     last.beta, None, None, coefs[-1], True, dz.view(B, S * cl, P), dgamma, dbeta)
+            grads[last.ig], grads[last.ibeta] = dgamma, dbeta
         else:
             dz = dout
-            if b is not None and need[3 + slots[-1]['b']]:
+            if last.b is not None and need[3 + last.ib]:
                 # (one workgroup per channel in a fixed order: ATen's two-axis reduction took 13 - 18 us)
-                grads[slots[-1]['b']] = backend.channel_sum(dz if S == 1 else dz.view(B, S * cl, P))
-        dx = None
-        pending = None          # (da, part) of the layer whose norm backward has not been applied yet
-        for l in range(L - 1, -1, -1):
-            w = per_layer[l][0]
-            cout, cin = w.shape[1], w.shape[2]
-            src = x if l == 0 else ys[l - 1]
-            src_coef = None if l == 0 else coefs[l - 1]
-            need_w = need[3 + slots[l]['w']]
-            if pending is not None:     # norm backward of this layer, with its weight gradient
-                dz, dw, dgamma, dbeta = _norm_backward_wgrad(
-                    backend, pending[0], ys[l], per_layer[l][2], coefs[l], pending[1], src, src_coef, need_w, ng=S,
-                    slots=(tslots[slots[l]['w']], tslots[slots[l]['g']], tslots[slots[l]['g'] + 1]))
-                grads[slots[l]['g']], grads[slots[l]['g'] + 1] = dgamma, dbeta
-                if dw is not None:
-                    grads[slots[l]['w']] = dw.view(per_layer[l][0].shape)
-                if 'b' in slots[l] and need[3 + slots[l]['b']]:
-                    grads[slots[l]['b']] = zero_bias(l)
-            elif need_w:
-                grads[slots[l]['w']] = _wgrad(backend, dz, src, src_coef, ng=S,
-                                              slot=tslots[slots[l]['w']]).view(per_layer[l][0].shape)
-            if l == 0:
-                if need[0]:
-                    if backend.pw_supported(cout, cin, P):
-                        dx = dz.new_empty(NB, cin, P)
-                        backend.pw_layer_forward(dz, w.transpose(1, 2), ng=S, y=dx)
-                    else:
-                        dx = torch.matmul(w.transpose(1, 2).unsqueeze(0), dz.view(B, S, cout, P)).view(NB, cin, P)
-                break
-            # gradient of the previous layer's activation (+ the reduction of its norm backward)
-            da = dz.new_empty(NB, cin, P)
-            part = backend.pw_dgrad_bn_reduce(dz, w.transpose(1, 2), ys[l - 1], coefs[l - 1], da, ng=S)
-            pending = (da, part)
+                grads[last.ib] = backend.channel_sum(dz if S == 1 else dz.view(B, S * cl, P))
+
+        def input_grad(dz, lay):
+            if not need[0]:
+                return None
+            cout, cin = lay.w.shape[1], lay.w.shape[2]
+            if not backend.pw_supported(cout, cin, P):
+                return torch.matmul(lay.w.transpose(1, 2).unsqueeze(0), dz.view(B, S, cout, P)).view(NB, cin, P)
+            dx = dz.new_empty(NB, cin, P)
+            backend.pw_layer_forward(dz, lay.w.transpose(1, 2), ng=S, y=dx)
+            return dx
+        dx = _chain_backward(backend, ctx, lays, x, ys, coefs, grads, len(lays) - 1, dz, ng=S, input_grad=input_grad)
+        for lay in lays:
+            if lay.bn is not None and lay.b is not None and need[3 + lay.ib]:
+                # the bias in front of a norm: gradient identically zero.
+                # With a slot in the flat gradient vector the answer is None: FlatTrainState.collect()
+                # zero-fills every parameter that got no gradient (one multi-tensor fill for all of
+                # them), so whatever an earlier step, another path or a loaded vector left in the slot
+                # is overwritten in every step.  Without a flat state: a zero tensor, as ATen returns
+                # (a None would make a per-parameter optimiser skip the parameter).
+                grads[lay.ib] = None if slots[lay.ib] is not None else torch.zeros_like(lay.b)
         return (dx, None, None) + tuple(grads)
 
 
@@ -1018,7 +1026,6 @@ def stack1d_supported(backend, x, shapes, norms, S=1):
     norm layer (or None) behind each conv; native training BatchNorm1d/2d with a folded ReLU,
     fp32, every forward and input-gradient product inside the built tiles, only the LAST layer
     may come without a norm."""
-    from .norm import FusedBNReLU1d, FusedBNReLU2d
     if not ENABLED or backend.name != 'hip' or x.dtype != torch.float32 or not torch.is_grad_enabled():
         return False
     P = x.shape[-1] if x.dim() == 3 else x.numel() // (x.shape[0] * x.shape[1])
@@ -1026,8 +1033,7 @@ def stack1d_supported(backend, x, shapes, norms, S=1):
         if norm is None:
             if i != len(shapes) - 1:
                 return False
-        elif not (isinstance(norm, (FusedBNReLU1d, FusedBNReLU2d)) and norm.fuse_relu and norm.training
-                  and norm.affine and norm.track_running_stats and norm.momentum is not None):
+        elif not _native_norm(norm, training=True):
             return False
         if not backend.pw_supported(cin, cout, P):
             return False
