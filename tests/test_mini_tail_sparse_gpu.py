@@ -5,7 +5,8 @@ nesie_pw_wgrad_sparse (a sparse product on the vector ALUs that leaves the dense
 float64, and bit for bit the dense weight gradient).
 
 Measured on MI355X: the relative L2 error of dW4 against float64 is the dense kernel's to the last digit
-(4.45e-8 ... 1.12e-7 over the eight shapes), the results being bit-equal."""
+(4.45e-8 ... 1.12e-7 over the eight shapes), the results being bit-equal.
+The whole MiniPointNet chain on this route against float64 autograd is in tests/test_fused_chains_fp64_gpu.py."""
 import os
 import subprocess
 import sys

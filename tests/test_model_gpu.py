@@ -1,4 +1,5 @@
-"""Detector path: HIP product path on the GPU vs the same model through the CPU oracle."""
+"""Detector path: HIP product path on the GPU vs the same model through the CPU oracle.
+The fused MLP chains it runs through have a float64 referee of their own, tests/test_fused_chains_fp64_gpu.py."""
 import copy
 
 import pytest

@@ -1,7 +1,9 @@
 """The fp32-MFMA pointwise-conv layer kernel (nesie_pw_layer_forward) and the fused shared-MLP
 functions built on it, against fp64 / module-by-module evaluations of the reference's
 ConvModule(Conv2d 1x1, BN2d, ReLU) chains (point_sa_module.py:277-289, 136-158;
-side_pooling_module.py:343-370)."""
+side_pooling_module.py:343-370).  The fused-vs-unfused comparisons here are between two float32 legs;
+their float64 referee, branch by branch and with no element excused, is
+tests/test_fused_chains_fp64_gpu.py."""
 import pytest
 import torch
 

@@ -3,7 +3,8 @@ module-by-module evaluation of the same modules (fused_mlp.ENABLED = False: conv
 and bias one operator at a time, as the reference does): VoteModule (vote_module.py:65-74, 85-147),
 ReliableConvBboxHead (reliable_conv_bbox_module.py:112-177), PointFPModule
 (point_fp_module.py:31-78), the quality head's score heads (side_pooling_module.py:55-78, 318).
-Outputs 1e-4 relative, running statistics, gradients of every parameter and of the input."""
+Outputs 1e-4 relative, running statistics, gradients of every parameter and of the input.
+The float64 referee of these chains, branch by branch, is tests/test_fused_chains_fp64_gpu.py."""
 import copy
 
 import pytest
