@@ -175,94 +175,167 @@ __global__ __launch_bounds__(TI_BLOCK) void three_interpolate_kernel(
 //
 //   out = w0 * T[j0] + w1 * T[j1] + w2 * T[j2]  (+ wx . rel)
 //
-// T is a POINT-major table (B, M, pitch): the three taps of a query are dense 256-byte rows
-// per 64 channels (lane = channel); a 64 x 64 tile turns through LDS and leaves as dense rows
-// along the query axis (lane = query).  With T = the seed features this is three_interpolate
-// in the segmented layout.  With T = F . W_f^T (the seed features already multiplied by the
+// T is a POINT-major table (B, M, pitch): the three taps of a query are dense rows of up to
+// 1 KB (a lane owns c / 64 consecutive channels); a (channels x 64 queries) tile turns through
+// LDS and leaves as dense rows along the query axis (lane = query).  With T = the seed
+// features this is three_interpolate in the segmented layout.  With T = F . W_f^T (the seed features already multiplied by the
 // feature columns of a MiniPointNet's first 1x1 conv, one column block per face: seg_off) and
 // wx = that conv's three xyz columns, it IS the first conv's output,
 //   W . cat[rel_xyz, blend(F)] = W_xyz . rel_xyz + blend(W_f . F)      (the conv is linear),
 // at ~1/250 of the multiply-adds and without ever storing the 259-channel feature tensor.
 constexpr int TS_Q = 64;  // queries per workgroup (one tile side; per_seg % 64 == 0)
+constexpr int BF_LD = TS_Q + 1;   // tile row pitch in floats: odd, so both tile phases meet no bank conflict
+typedef float bf_f2 __attribute__((ext_vector_type(2)));
+constexpr int BF_NQ = 8;          // queries whose taps are in flight before the first is consumed
 
+// CPT = channels per lane: a workgroup covers CW = 64 * CPT channels (c > 256 runs as chunks of 256
+// along blockIdx.y, a remainder as a launch of its own starting at channel `cb`).
+//  * A wave keeps its 16 consecutive queries for all CW channels.  Lane l & 15 reads query l's
+//    three (clamped seed, weight, rel) once; v_readlane makes them wave-uniform, so a tap is a
+//    scalar row base plus one per-lane offset and moves as ONE load of 4 * CPT bytes per lane (a
+//    1 KB row per instruction at CPT = 4), and the weights and rel multiply from scalar registers.
+//  * The 3 * BF_NQ loads of BF_NQ queries are issued back to back before the first is consumed;
+//    `wx` and the statistics are template parameters, so nothing branches inside the loop.
+//  * Channel lane * CPT + e sits in tile row e * 64 + lane: the 64 lanes of a tile write land in 64
+//    different banks, and so do the 4 rows x 16 lanes of a row read of the store phase.
+// The arithmetic is the tile kernel's of rounds 1-6, rounding by rounding:
+//   v = (w0 a0 + w1 a1) + w2 a2   [+ x0 r0, + x1 r1, + x2 r2, added left to right], every product
+//   rounded on its own; per (channel, tile) the sums of v and of v * v run over a wave's 16 queries
+//   in ascending order from 0, and the four waves' sums combine as (0 + 1) + (2 + 3).
+template <int CPT, bool WX, bool STAT>
 __global__ __launch_bounds__(256) void blend_fwd_kernel(
-    int c, int m, int n, int segs, int seg_len, int c_total, int c_offset, int pitch,
+    int c, int cb, int m, int n, int segs, int seg_len, int c_total, int c_offset, int pitch,
     int seg_off, const float *__restrict__ table, const int *__restrict__ idx,
     const float *__restrict__ weight, const float *__restrict__ rel,
     const float *__restrict__ wx, float *__restrict__ out, float *__restrict__ stat_partial,
-    int nt, int nb) {
-  __shared__ float tile[64][TS_Q + 1];
-  __shared__ float red[4][64][2];
-  __shared__ int sj[TS_Q][3];
-  __shared__ float sw[TS_Q][3];
-  __shared__ float sr[TS_Q][3];
+    int nb) {
+#pragma clang fp contract(off)
+  constexpr int CW = CPT * 64;
+  extern __shared__ float bf_lds[];
+  float *tile = bf_lds;                      // [CW][BF_LD]
+  float *red = bf_lds + CW * BF_LD;          // [4][CW][2]  (STAT only)
   // 1-D grid with the scene fastest: workgroup i runs on XCD i % 8, so with B = 8 every scene's
   // table rows are gathered through ONE XCD's L2 instead of all eight
   const int bi = blockIdx.x % nb;
   const int q0 = (blockIdx.x / nb) * TS_Q;  // output order: s * per_seg + k * seg_len + g
+  const int c0 = cb + blockIdx.y * CW;
   const int per_seg = n / segs;
   const int sg = q0 / per_seg, r0 = q0 - sg * per_seg;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (threadIdx.x < TS_Q) {
-    const int r = r0 + threadIdx.x;
+  // the taps of this wave's 16 queries: lane l (and l + 16, l + 32, l + 48) holds query wv * 16 + l
+  int pj[3];
+  float pw[3], pr[3];
+  {
+    const int r = r0 + wv * 16 + (lane & 15);
     const int k = r / seg_len, g = r - k * seg_len;
     const size_t p = (size_t)bi * n + (size_t)(k * segs + sg) * seg_len + g;
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      int j = idx[p * 3 + t];
-      sj[threadIdx.x][t] = j < 0 ? 0 : (j >= m ? m - 1 : j);
-      sw[threadIdx.x][t] = weight[p * 3 + t];
-      sr[threadIdx.x][t] = rel ? rel[p * 3 + t] : 0.f;
+      const int j = idx[p * 3 + t];
+      pj[t] = j < 0 ? 0 : (j >= m ? m - 1 : j);
+      pw[t] = weight[p * 3 + t];
+      pr[t] = WX ? rel[p * 3 + t] : 0.f;
+    }
+  }
+  const float *feat = table + (size_t)bi * m * pitch + (size_t)sg * seg_off + c0;   // uniform
+  const unsigned voff = (unsigned)(lane * CPT * 4);
+  float x[CPT][3] = {};
+  if (WX) {
+    __builtin_memcpy(&x[0][0], wx + ((size_t)sg * c + c0 + lane * CPT) * 3, sizeof(x));
+  }
+  // Two channels per instruction where CPT allows: v_pk_mul_f32 / v_pk_add_f32 round each half like
+  // the scalar forms, and contraction is off, so no product is fused into its add.
+  constexpr int CP2 = CPT / 2;
+  bf_f2 s2[CP2 ? CP2 : 1], q2[CP2 ? CP2 : 1];
+  float s1 = 0.f, q1 = 0.f;                          // the odd channel (CPT = 1, 3)
+#pragma unroll
+  for (int e = 0; e < CP2; ++e) s2[e] = q2[e] = bf_f2{0.f, 0.f};
+#pragma unroll
+  for (int i0 = 0; i0 < 16; i0 += BF_NQ) {
+    float a[BF_NQ][3][CPT];
+#pragma unroll
+    for (int i = 0; i < BF_NQ; ++i)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const int j = __builtin_amdgcn_readlane(pj[t], i0 + i);
+        const float *row = feat + (size_t)j * pitch;                                // uniform
+        __builtin_memcpy(a[i][t], (const char *)row + voff, CPT * 4);
+      }
+    // (without this the scheduler sinks every load to its use to save registers that the LDS-bound
+    // residency cannot use: three loads in flight and a full wait per query)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < BF_NQ; ++i) {
+      const int qi = wv * 16 + i0 + i;
+      float sw[3], sr[3];
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        sw[t] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pw[t]), i0 + i));
+        sr[t] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pr[t]), i0 + i));
+      }
+      // products rounded one by one, summed left to right (three_interpolate_cuda.cu:33-34)
+      auto blend = [&](auto a0, auto a1, auto a2, auto x0, auto x1, auto x2) {
+        auto v = (a0 * sw[0] + a1 * sw[1]) + a2 * sw[2];
+        if (WX) v = ((v + x0 * sr[0]) + x1 * sr[1]) + x2 * sr[2];
+        return v;
+      };
+#pragma unroll
+      for (int h = 0; h < CP2; ++h) {
+        const int e = 2 * h;
+        const bf_f2 v = blend(bf_f2{a[i][0][e], a[i][0][e + 1]}, bf_f2{a[i][1][e], a[i][1][e + 1]},
+                              bf_f2{a[i][2][e], a[i][2][e + 1]}, bf_f2{x[e][0], x[e + 1][0]},
+                              bf_f2{x[e][1], x[e + 1][1]}, bf_f2{x[e][2], x[e + 1][2]});
+        tile[(e * 64 + lane) * BF_LD + qi] = v.x;
+        tile[((e + 1) * 64 + lane) * BF_LD + qi] = v.y;
+        if (STAT) {
+          s2[h] = s2[h] + v;
+          q2[h] = q2[h] + v * v;
+        }
+      }
+      if (CPT & 1) {
+        constexpr int e = CPT - 1;
+        const float v = blend(a[i][0][e], a[i][1][e], a[i][2][e], x[e][0], x[e][1], x[e][2]);
+        tile[(e * 64 + lane) * BF_LD + qi] = v;
+        if (STAT) {
+          s1 = s1 + v;
+          q1 = q1 + v * v;
+        }
+      }
+    }
+  }
+  if (STAT) {
+#pragma unroll
+    for (int e = 0; e < CPT; ++e) {
+      const bool odd = (CPT & 1) && e == CPT - 1;
+      red[((wv * CW) + e * 64 + lane) * 2] = odd ? s1 : s2[e / 2][e & 1];
+      red[((wv * CW) + e * 64 + lane) * 2 + 1] = odd ? q1 : q2[e / 2][e & 1];
     }
   }
   __syncthreads();
-  const float *feat = table + (size_t)bi * m * pitch + (size_t)sg * seg_off;
-  float *dst = out + (((size_t)bi * segs + sg) * c_total + c_offset) * per_seg + r0;
-  for (int c0 = 0; c0 < c; c0 += 64) {
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    if (wx) {
-      const float *wr = wx + ((size_t)sg * c + c0 + lane) * 3;
-      x0 = wr[0]; x1 = wr[1]; x2 = wr[2];
-    }
-    // wave wv blends queries wv*16 .. wv*16+15 for channels c0 .. c0+63 (lane = channel)
-    float a_s = 0.f, a_q = 0.f;
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-      const int qi = wv * 16 + i;
-      const float *f = feat + c0 + lane;
-      const float a0 = f[(size_t)sj[qi][0] * pitch], a1 = f[(size_t)sj[qi][1] * pitch],
-                  a2 = f[(size_t)sj[qi][2] * pitch];
-      // products rounded one by one, summed left to right (three_interpolate_cuda.cu:33-34)
-      float v = __fadd_rn(__fadd_rn(__fmul_rn(sw[qi][0], a0), __fmul_rn(sw[qi][1], a1)),
-                          __fmul_rn(sw[qi][2], a2));
-      if (wx)
-        v = __fadd_rn(__fadd_rn(__fadd_rn(v, __fmul_rn(x0, sr[qi][0])), __fmul_rn(x1, sr[qi][1])),
-                      __fmul_rn(x2, sr[qi][2]));
-      tile[lane][qi] = v;
-      a_s += v; a_q += v * v;
-    }
-    if (stat_partial) { red[wv][lane][0] = a_s; red[wv][lane][1] = a_q; }
-    __syncthreads();
-    // wave wv stores channels c0 + wv*16 .. +15: four 256-byte rows per instruction (16 lanes x
-    // 16 bytes each) instead of one -- a quarter of the store instructions for the same bytes
+  // wave wv stores tile rows wv * 16 CPT .. + 16 CPT - 1: four 256-byte rows per instruction (16
+  // lanes x 16 bytes each) instead of one -- a quarter of the store instructions for the same bytes.
+  // NON-TEMPORAL: the output is written once and is far larger than L2; plain stores allocate there
+  // and push out the table rows the gather lives on (measured at the step's shapes with
+  // tools/blend_bench.py fwd-side / fwd-box: 154 / 92 us plain, 103 / 67 us non-temporal)
+  float *dst = out + (((size_t)bi * segs + sg) * c_total + c_offset + c0) * per_seg + r0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ch = wv * 16 + i * 4 + (lane >> 4), q4 = (lane & 15) * 4;
-      const float4 v = make_float4(tile[ch][q4], tile[ch][q4 + 1], tile[ch][q4 + 2], tile[ch][q4 + 3]);
-      float *o = dst + (size_t)(c0 + ch) * per_seg + q4;
-      if (nt) st4<true>(o, v); else st4<false>(o, v);
-    }
-    if (stat_partial && wv == 0) {
-      // (sum, sum of squares) of this tile per stacked channel, for the norm layer that follows:
-      // partial[(chan * nslice + slice) * 2], nslice = B * per_seg / 64 (bn.hip's layout)
-      const float ss = (red[0][lane][0] + red[1][lane][0]) + (red[2][lane][0] + red[3][lane][0]);
-      const float qq = (red[0][lane][1] + red[1][lane][1]) + (red[2][lane][1] + red[3][lane][1]);
-      const int nslice = nb * (per_seg / TS_Q);
-      const int slice = bi * (per_seg / TS_Q) + r0 / TS_Q;
-      float *pd = stat_partial + ((size_t)(sg * c + c0 + lane) * nslice + slice) * 2;
-      pd[0] = ss; pd[1] = qq;
-    }
-    __syncthreads();
+  for (int i = 0; i < 4 * CPT; ++i) {
+    const int row = wv * (16 * CPT) + i * 4 + (lane >> 4), q4 = (lane & 15) * 4;
+    const int ch = (row & 63) * CPT + (row >> 6);
+    const float *tr = tile + row * BF_LD + q4;
+    st4<true>(dst + (size_t)ch * per_seg + q4, make_float4(tr[0], tr[1], tr[2], tr[3]));
+  }
+  if (STAT && threadIdx.x < CW) {
+    // (sum, sum of squares) of this tile per stacked channel, for the norm layer that follows:
+    // partial[(chan * nslice + slice) * 2], nslice = B * per_seg / 64 (bn.hip's layout)
+    const int row = threadIdx.x, ch = (row & 63) * CPT + (row >> 6);
+    const float *rd = red + row * 2;
+    const float ss = (rd[0] + rd[CW * 2]) + (rd[2 * CW * 2] + rd[3 * CW * 2]);
+    const float qq = (rd[1] + rd[CW * 2 + 1]) + (rd[2 * CW * 2 + 1] + rd[3 * CW * 2 + 1]);
+    const int nslice = nb * (per_seg / TS_Q);
+    const int slice = bi * (per_seg / TS_Q) + r0 / TS_Q;
+    float *pd = stat_partial + ((size_t)(sg * c + c0 + ch) * nslice + slice) * 2;
+    pd[0] = ss; pd[1] = qq;
   }
 }
 
@@ -793,6 +866,34 @@ static int blend_check(const char *W, int b, int c, int m, int n, int segs, int 
   return NESIE_OK;
 }
 
+// `chunks` workgroup columns of 64 * CPT channels each, the first at channel cb.  The tile and the
+// statistics scratch are dynamic LDS (73 KB at CPT = 4: two workgroups per CU).
+template <int CPT>
+static void blend_fwd_launch(int chunks, int cb, int b, int c, int m, int n, int segs, int seg_len,
+                             int c_total, int c_offset, int pitch, int seg_off, const float *table,
+                             const int *idx, const float *weight, const float *rel, const float *wx,
+                             float *out, float *stat_partial, hipStream_t s) {
+  if (chunks <= 0) return;
+  constexpr int CW = CPT * 64;
+  const size_t lds = (size_t)CW * (BF_LD + 4 * 2) * sizeof(float);
+  const dim3 grid((unsigned)((n / TS_Q) * b), (unsigned)chunks);
+#define BF(WXF, STF)                                                                              \
+  do {                                                                                            \
+    static bool attr = false;                                                                     \
+    if (!attr) {                                                                                  \
+      (void)hipFuncSetAttribute((const void *)blend_fwd_kernel<CPT, WXF, STF>,                    \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
+      attr = true;                                                                                \
+    }                                                                                             \
+    hipLaunchKernelGGL((blend_fwd_kernel<CPT, WXF, STF>), grid, dim3(256), lds, s, c, cb, m, n,   \
+                       segs, seg_len, c_total, c_offset, pitch, seg_off, table, idx, weight, rel, \
+                       wx, out, stat_partial, b);                                                 \
+  } while (0)
+  if (wx) { if (stat_partial) BF(true, true); else BF(true, false); }
+  else { if (stat_partial) BF(false, true); else BF(false, false); }
+#undef BF
+}
+
 extern "C" int nesie_blend_conv_forward(int b, int c, int m, int n, const float *table,
                                         int pitch, int seg_off, const int *idx,
                                         const float *weight, const float *rel, const float *wx,
@@ -808,11 +909,17 @@ extern "C" int nesie_blend_conv_forward(int b, int c, int m, int n, const float 
     set_error("%s: stat_partial needs c %% 64 == 0 and %d-multiple faces", W, TS_Q);
     return NESIE_ERR_UNSUPPORTED;
   }
-  if (c % 64 == 0 && (n / segs) % TS_Q == 0)
-    hipLaunchKernelGGL(blend_fwd_kernel, dim3((n / TS_Q) * b), dim3(256), 0, (hipStream_t)stream, c,
-                       m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table, idx, weight,
-                       rel, wx, out, stat_partial, 0, b);
-  else
+  if (c % 64 == 0 && (n / segs) % TS_Q == 0) {
+    NESIE_REQUIRE((long long)(n / TS_Q) * b < (1ll << 31) && ((uintptr_t)out & 15) == 0, W);   // (float4 row stores)
+    // whole chunks of 256 channels along grid y, then the 64 / 128 / 192 that remain
+    blend_fwd_launch<4>(c / 256, 0, b, c, m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table,
+                        idx, weight, rel, wx, out, stat_partial, (hipStream_t)stream);
+    const int cb = c / 256 * 256, left = (c - cb) / 64;
+#define REST(N) blend_fwd_launch<N>(1, cb, b, c, m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table, \
+                                    idx, weight, rel, wx, out, stat_partial, (hipStream_t)stream)
+    if (left == 1) REST(1); else if (left == 2) REST(2); else if (left == 3) REST(3);
+#undef REST
+  } else
     hipLaunchKernelGGL(blend_fwd_generic_kernel, dim3(cdiv(n, TI_BLOCK), cdiv(c, TI_CH), b),
                        dim3(TI_BLOCK), 0, (hipStream_t)stream, c, m, n, segs, seg_len, c_total,
                        c_offset, pitch, seg_off, table, idx, weight, rel, wx, out);
