@@ -18,14 +18,20 @@ re-derived with the same fused multiply-add the forward's operand load used).
 Same function as the module-by-module path (which stays the CPU checker's and serves shapes the
 kernels are not built for); differences are fp32 summation order and fma-vs-mul/add rounding.
 
-How the host side is laid out: the two chain functions (``SAStackFn``, ``Stack1dFn``) describe their
-layers once as ``_Layer`` records (``_chain_layout``: which of the function's tensors is a layer's
-weight, bias, scale, shift -- the same positions address the gradient slots and the returned
-gradients), store and fetch their state through ``_save_chain`` / ``_saved_chain``, and share ONE
-walk back through the layers (``_chain_backward``); what differs between them -- how the top of
-the chain is entered, SA1's rebuilt first activation, the coordinate rows of the input gradient,
-the zero bias gradient -- stays in the two ``backward``s.  A layer that leaves through a max over
-groups of positions is ``_pooled_layer`` everywhere.  Which launches each function issues, in
+How the host side is laid out: the three chain functions (``SAStackFn``, ``Stack1dFn``, ``MiniTailFn``)
+describe their layers once as ``_Layer`` records (``_chain_layout``: which of the function's tensors is
+a layer's weight, bias, scale, shift -- the same positions address the gradient slots and the
+returned gradients, behind however many arguments the function has in front of them), store and
+fetch their state through ``_save_chain`` / ``_saved_chain``, and share ONE walk back through the
+layers (``_chain_backward``); what differs between them -- how the top of the chain is entered, SA1's
+rebuilt first activation, the coordinate rows of the input gradient, the zero bias gradient --
+stays in the ``backward``s.  Particular to the MiniPointNet tail: the row bias that joins its first
+layer's output (its gradient leaves from that layer's norm backward, ``rb_group``), its two ways in
+at the top (the max-pool's entries, or the expanded dense gradient), and W_l, a split view that
+gets no slot.  The two head functions (``MiniHeadFn``, ``BlendMiniHeadFn``) are a norm without a conv
+in front of one conv, not a chain: they share ``_mini_head_backward`` / ``_first_norm_apply`` and name
+their three parameters' positions once (``_GAMMA0, _BETA0, _W3``).  A layer that leaves through a max
+over groups of positions is ``_pooled_layer`` everywhere.  Which launches each function issues, in
 which order and over which buffers is pinned without a GPU by tests/test_fused_mlp_trace_cpu.py.
 """
 
@@ -116,7 +122,7 @@ def _wgrad_aten(backend, dy, x, x_coef, ng):
 
 
 def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_w, ng=1, need_dz=True,
-                         slots=(None, None, None)):
+                         slots=(None, None, None), rb_group=None):
     """The backward of relu(bn(z)) given da (its gradient) and the reduction partials the
     input-gradient launch left, and the weight gradient dz . act(src)^T of the conv that produced z:
     -> (dz, dw | None, dgamma, dbeta).  One launch where the layer kernel's weight gradient serves
@@ -124,17 +130,25 @@ def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_
     da), the apply pass + ``_wgrad`` otherwise.  ``need_dz`` False (the layer's input needs no
     gradient) and a skinny input (Cin <= 8, the first layer of SA1): ``nesie_conv_wgrad_bn`` forms
     dz on its load and never writes it -> dz None.  ``slots`` = gradient slots of (weight, gamma,
-    beta): the kernels write there."""
+    beta): the kernels write there.  ``rb_group`` = G: the forward added a row bias per group of G
+    positions to z (the MiniPointNet tail); its gradient (nb, co, p / G) leaves from the launch that forms
+    dz and is returned as a fifth value (the one-launch form serves G = 16 and 64, adding into zeros at 64)."""
     nb, co, p = da.shape
     ci = src.shape[1]
     s_w, s_g, s_b = slots
     dgamma, dbeta = _dst(s_g, da, ng * co), _dst(s_b, da, ng * co)
-    if FOLD_NORM_BWD and need_w and backend.pw_wgrad_bn_supported(co, ci, p):
+    fold = FOLD_NORM_BWD and need_w and rb_group in (None, 16, 64) and backend.pw_wgrad_bn_supported(co, ci, p)
+    d_rb, out = None, (dgamma, dbeta)
+    if rb_group:
+        d_rb = (da.new_zeros if fold and rb_group == 64 else da.new_empty)(nb, co, p // rb_group)
+        out += (d_rb,)
+    if fold:
         dw = _dst(s_w, da, ng, co, ci)
-        backend.pw_wgrad_bn_backward(da, z, coef, gamma, part, src, da, dw, dgamma, dbeta, ng=ng,
-                                     x_coef=src_coef, final=slots[0] is not None)
-        return da, dw, dgamma, dbeta
-    if FOLD_NORM_BWD and need_w and not need_dz and ng == 1 and ci <= 8 and backend.conv_wgrad_supported(co, ci):
+        backend.pw_wgrad_bn_backward(da, z, coef, gamma, part, src, da, dw, dgamma, dbeta, ng=ng, x_coef=src_coef,
+                                     d_row_bias=d_rb, group=rb_group or 0, final=s_w is not None)
+        return (da, dw) + out
+    if (FOLD_NORM_BWD and need_w and not need_dz and not rb_group and ng == 1 and ci <= 8
+            and backend.conv_wgrad_supported(co, ci)):
         bnb = backend.pw_bnb_coef(part, coef, gamma, float(nb) * float(p), dgamma, dbeta)
         dw = _dst(s_w, da, co, ci)
         backend.conv_wgrad(da, src, dw, x_coef=src_coef, x_relu=src_coef is not None, bn_z=z, bnb=bnb)
@@ -142,15 +156,23 @@ def _norm_backward_wgrad(backend, da, z, gamma, coef, part, src, src_coef, need_
     dz = torch.empty_like(da)
     b = nb // ng
     backend.bn_relu_backward_apply(da.view(b, ng * co, p), z.view(b, ng * co, p), gamma, None, coef, part,
-                                   dz.view(b, ng * co, p), dgamma, dbeta)
+                                   dz.view(b, ng * co, p), dgamma, dbeta,
+                                   d_row_bias=d_rb.view(b, ng * co, -1) if rb_group else None, group=rb_group)
     dw = _wgrad(backend, dz, src, src_coef, ng=ng, slot=s_w) if need_w else None
-    return dz, dw, dgamma, dbeta
+    return (dz, dw) + out
 
 
 def _take_slots(ctx, first_index, tensors):
-    """Gradient slots of ``tensors`` = the arguments of ``ctx``'s forward from ``first_index`` on (None
-    entries are passed over) -- only for those whose gradient a backward will be asked for."""
+    """Gradient slots of ``tensors`` = the arguments of ``ctx``'s forward from ``first_index`` on (negative:
+    counted from the back; None entries are passed over) -- only for those whose gradient a backward
+    will be asked for."""
     return [grad_slots.take(t) if ctx.needs_input_grad[first_index + j] else None for j, t in enumerate(tensors)]
+
+
+def _returned(ctx, inputs, params):
+    """What a backward returns: the gradients of its leading ``inputs``, None for every argument
+    between them and the trailing ``params``, then theirs."""
+    return tuple(inputs) + (None,) * (len(ctx.needs_input_grad) - len(inputs) - len(params)) + tuple(params)
 
 
 def _pool_group(G):
@@ -196,12 +218,12 @@ class Stack1dLayer:
         self.bias, self.bn = bool(bias), bn
 
 
-# One layer of a chain function (SAStackFn, Stack1dFn).  ``iw, ib, ig, ibeta``: where its weight,
-# conv bias, norm scale and shift sit among the function's ``*tensors`` (None = the layer has none)
-# -- which is also where their gradients sit in what the backward returns behind its three leading
-# Nones, and their slots in ``ctx.slots``; ``bn`` = the norm's (running_mean, running_var, momentum,
-# eps) or None.  The positions are static and live on ``ctx``; ``w, b, gamma, beta`` are filled in by
-# ``_bind`` from the forward's arguments or from the saved tensors.
+# One layer of a chain function (SAStackFn, Stack1dFn, MiniTailFn).  ``iw, ib, ig, ibeta``: where its
+# weight, conv bias, norm scale and shift sit among the function's trailing tensors (None = the layer
+# has none) -- which is also where their gradients sit in what the backward returns behind the
+# ``ctx.lead`` entries of its leading arguments, and their slots in ``ctx.slots``; ``bn`` = the norm's
+# (running_mean, running_var, momentum, eps) or None.  The positions are static and live on ``ctx``;
+# ``w, b, gamma, beta`` are filled in by ``_bind`` from the forward's arguments or from the saved tensors.
 _Layer = namedtuple('_Layer', 'bn iw ib ig ibeta w b gamma beta', defaults=(None,) * 4)
 
 
@@ -223,14 +245,17 @@ def _bind(chain, tensors):
     return [lay._replace(w=at(lay.iw), b=at(lay.ib), gamma=at(lay.ig), beta=at(lay.ibeta)) for lay in chain]
 
 
-def _save_chain(ctx, chain, head, ys, coefs, tensors):
+def _save_chain(ctx, chain, head, ys, coefs, tensors, no_slot=()):
     """What a chain's backward needs: ``head`` (the input and whatever else the function keeps), per
     layer the raw conv output and the folded norm coefficients (None where there is none), the
-    layers' tensors -- and the gradient slots of the tensors whose gradient a kernel (or a fill)
+    layers' tensors -- the LAST arguments of the function's forward; ``ctx.lead`` counts the ones in
+    front of them -- and the gradient slots of the tensors whose gradient a kernel (or a fill)
     writes: weights, norm scales / shifts, and the identically-zero bias in front of a norm (a plain
-    conv's bias gradient is a reduction of its own: nothing to gain there)."""
-    plain_bias = {lay.ib for lay in chain if lay.bn is None}
-    ctx.slots = _take_slots(ctx, 3, [None if i in plain_bias else t for i, t in enumerate(tensors)])
+    conv's bias gradient is a reduction of its own: nothing to gain there).  ``no_slot``: positions
+    among ``tensors`` whose gradient is somebody else's to place."""
+    skip = {lay.ib for lay in chain if lay.bn is None} | set(no_slot)
+    ctx.lead = len(ctx.needs_input_grad) - len(tensors)
+    ctx.slots = _take_slots(ctx, ctx.lead, [None if i in skip else t for i, t in enumerate(tensors)])
     ctx.chain, ctx.n_head = chain, len(head)
     ctx.save_for_backward(*head, *ys, *coefs, *tensors)
 
@@ -248,7 +273,7 @@ def _transposed(w):
 
 
 def _chain_backward(backend, ctx, lays, x, ys, coefs, grads, top, dz, pending=None, ng=1, input_grad=None,
-                    bottom=0):
+                    bottom=0, rb_group=None):
     """The walk from layer ``top`` down through a chain: per layer the norm backward and the weight
     gradient, then the input-gradient launch that also leaves the reduction of the next norm
     backward.  It is entered with ``dz`` = the gradient of layer ``top``'s raw output, or with
@@ -256,21 +281,25 @@ def _chain_backward(backend, ctx, lays, x, ys, coefs, grads, top, dz, pending=No
     backward, not applied yet.  Parameter gradients go into ``grads`` at the layers' positions (written
     into ``ctx.slots`` where there are any).  At layer 0 it returns ``input_grad(dz, layer)``; without
     an ``input_grad`` nobody reads the first layer's dz and it may never be written.  ``bottom`` > 0:
-    the walk ends in front of layer ``bottom - 1`` and returns that layer's pending."""
-    need, slots = ctx.needs_input_grad[3:], ctx.slots
+    the walk ends in front of layer ``bottom - 1`` and returns that layer's pending.  ``rb_group`` = G:
+    layer 0's forward added a row bias per group of G positions; its gradient is ``input_grad``'s
+    third argument."""
+    need, slots = ctx.needs_input_grad[ctx.lead:], ctx.slots
+    d_rb = ()
     for l in range(top, bottom - 1, -1):
         lay = lays[l]
         src, src_coef = (x, None) if l == 0 else (ys[l - 1], coefs[l - 1])
         if pending is not None:     # norm backward of this layer, with its weight gradient
-            dz, dw, grads[lay.ig], grads[lay.ibeta] = _norm_backward_wgrad(
+            dz, dw, grads[lay.ig], grads[lay.ibeta], *d_rb = _norm_backward_wgrad(
                 backend, pending[0], ys[l], lay.gamma, coefs[l], pending[1], src, src_coef, need[lay.iw], ng=ng,
-                need_dz=l > 0 or input_grad is not None, slots=(slots[lay.iw], slots[lay.ig], slots[lay.ibeta]))
+                need_dz=l > 0 or input_grad is not None, slots=(slots[lay.iw], slots[lay.ig], slots[lay.ibeta]),
+                rb_group=None if l else rb_group)
             if dw is not None:
                 grads[lay.iw] = dw.view(lay.w.shape)
         elif need[lay.iw]:
             grads[lay.iw] = _wgrad(backend, dz, src, src_coef, ng=ng, slot=slots[lay.iw]).view(lay.w.shape)
         if l == 0:
-            return None if input_grad is None else input_grad(dz, lay)
+            return None if input_grad is None else input_grad(dz, lay, *d_rb)
         # gradient of the previous layer's activation (+ the reduction of its norm backward)
         da = dz.new_empty(dz.shape[0], src.shape[1], dz.shape[2])
         part = backend.pw_dgrad_bn_reduce(dz, _transposed(lay.w), src, src_coef, da, ng=ng)
@@ -368,7 +397,7 @@ class SAStackFn(Function):
         if ctx.tail:
             # last layer without its dense tensors: yl is the raw extremum per (channel, group)
             wl = last.w
-            need_w = need[3 + last.iw]
+            need_w = need[ctx.lead + last.iw]
             dwl = _dst(slots[last.iw], g, cl, wl.shape[1]) if need_w else None
             pending = backend.pool_tail_backward(g.contiguous(), pooled, yl, argmax, coefs[-1], last.gamma,
                                                  wl.reshape(cl, wl.shape[1]), ys[-2], coefs[-2], ns,
@@ -402,7 +431,7 @@ class SAStackFn(Function):
         out = _chain_backward(backend, ctx, lays, x3, ys, coefs, grads, top, dy, pending,
                               input_grad=input_grad if need[0] else None, bottom=2 if ctx.k4 else 0)
         if not ctx.k4:
-            return (out, None, None) + tuple(grads)
+            return _returned(ctx, (out,), grads)
         # second layer over the rebuilt first activation: its fused norm backward + weight
         # gradient and ONLY the reductions of its input gradient -- they determine the
         # first layer's norm backward and weight gradient (nesie_k4_first_layer_wgrad) --
@@ -422,7 +451,7 @@ class SAStackFn(Function):
         dw0 = _dst(slots[first.iw], g, cin, c0)
         backend.k4_first_layer_wgrad(k4_mom, w0c, bnb, g_part, dw0)
         grads[first.iw], grads[first.ig], grads[first.ibeta] = dw0.view_as(first.w), dgamma0, dbeta0
-        return (None, None, None) + tuple(grads)
+        return _returned(ctx, (), grads)
 
 
 def _pooled_tail_whole(cin, cout):
@@ -635,9 +664,17 @@ def _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3):
     return c, g, arg, coef0
 
 
-def _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, G, need_w3, slot_w3=None):
-    """-> (da0 (B*S, H0, P) = gradient of relu(bn0(c0)), reduction partials, dw3)."""
+# MiniHeadFn and BlendMiniHeadFn take different inputs and END in the same three parameters: where these
+# sit in ``needs_input_grad``, in ``ctx.slots`` and in the returned gradients is counted from the back.
+# (The norm without a conv in front of W3 is no ``_Layer``: the two heads share the helpers below.)
+_GAMMA0, _BETA0, _W3 = -3, -2, -1
+
+
+def _mini_head_backward(backend, ctx, dc, dg, c0, coef0, arg, gamma0, w3):
+    """-> (da0 (B*S, H0, P) = gradient of relu(bn0(c0)), reduction partials, where the first norm's
+    backward writes dgamma and dbeta, dw3)."""
     B, S, H0, P = c0.shape
+    G = ctx.G
     half = w3.shape[1]
     # (MiniTailFn.backward hands over a buffer it has just allocated and marks the tensor object:
     # that one is ours to write into; anything else is copied first)
@@ -657,12 +694,12 @@ def _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, G, need_w3,
     x0 = c0.view(B * S, H0, P)
     dcf = dc.view(B * S, half, P)
     dw3 = None
-    if need_w3:
+    if ctx.needs_input_grad[_W3]:
         # per-net weight gradient: the S nets are the S strided batch subsets
-        dw3 = _wgrad(backend, dcf, x0, coef0, ng=S, slot=slot_w3)
+        dw3 = _wgrad(backend, dcf, x0, coef0, ng=S, slot=ctx.slots[_W3])
     da0 = c0.new_empty(B * S, H0, P)
     part = backend.pw_dgrad_bn_reduce(dcf, w3.transpose(1, 2), x0, coef0, da0, ng=S)
-    return da0, part, dw3
+    return da0, part, _dst(ctx.slots[_GAMMA0], c0, S * H0), _dst(ctx.slots[_BETA0], c0, S * H0), dw3
 
 
 def _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta):
@@ -685,7 +722,7 @@ class MiniHeadFn(Function):
         c0 = c0.contiguous()
         c, g, arg, coef0 = _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3)
         ctx.G = G
-        ctx.slots = _take_slots(ctx, 4, (gamma0, beta0, w3))
+        ctx.slots = _take_slots(ctx, _GAMMA0, (gamma0, beta0, w3))
         ctx.save_for_backward(c0, coef0, arg, gamma0, beta0, w3)
         ctx.mark_non_differentiable(arg)
         return c, g
@@ -694,12 +731,9 @@ class MiniHeadFn(Function):
     def backward(ctx, dc, dg):
         c0, coef0, arg, gamma0, beta0, w3 = ctx.saved_tensors
         backend = backend_for(c0)
-        B, S, H0, P = c0.shape
-        da0, part, dw3 = _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, ctx.G,
-                                             ctx.needs_input_grad[6], ctx.slots[2])
-        dgamma, dbeta = _dst(ctx.slots[0], c0, S * H0), _dst(ctx.slots[1], c0, S * H0)
+        da0, part, dgamma, dbeta, dw3 = _mini_head_backward(backend, ctx, dc, dg, c0, coef0, arg, gamma0, w3)
         dc0 = _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta)
-        return dc0, None, None, None, dgamma, dbeta, dw3
+        return _returned(ctx, (dc0,), (dgamma, dbeta, dw3))
 
 
 class BlendMiniHeadFn(Function):
@@ -727,7 +761,7 @@ class BlendMiniHeadFn(Function):
                                    stat_partial=c0_part)
         c, g, arg, coef0 = _mini_head_forward(backend, c0, c0_part, bufs, G, gamma0, beta0, w3)
         ctx.G, ctx.dims = G, (segs, seg_len, b, m, pitch, h)
-        ctx.slots = _take_slots(ctx, 9, (gamma0, beta0, w3))
+        ctx.slots = _take_slots(ctx, _GAMMA0, (gamma0, beta0, w3))
         ctx.save_for_backward(c0, coef0, arg, gamma0, w3, idx, weight, rel)
         ctx.mark_non_differentiable(arg)
         return c, g
@@ -738,9 +772,7 @@ class BlendMiniHeadFn(Function):
         segs, seg_len, b, m, pitch, h = ctx.dims
         backend = backend_for(c0)
         B, S, H0, P = c0.shape
-        da0, part, dw3 = _mini_head_backward(backend, dc, dg, c0, coef0, arg, gamma0, w3, ctx.G,
-                                             ctx.needs_input_grad[11], ctx.slots[2])
-        dgamma, dbeta = _dst(ctx.slots[0], c0, S * H0), _dst(ctx.slots[1], c0, S * H0)
+        da0, part, dgamma, dbeta, dw3 = _mini_head_backward(backend, ctx, dc, dg, c0, coef0, arg, gamma0, w3)
         # (the staged backward writes every row; the atomic form adds into zeros)
         d_table = (c0.new_empty if backend.blend_backward_writes_table(h, idx.shape[1], segs, m) else c0.new_zeros)(b, m, pitch)
         d_wx = c0.new_empty(segs, h, 3)          # (written, not accumulated)
@@ -751,7 +783,7 @@ class BlendMiniHeadFn(Function):
         else:       # A/B switch: the separate apply pass
             dc0 = _first_norm_apply(backend, da0, part, c0, coef0, gamma0, dgamma, dbeta)
             backend.blend_conv_backward(dc0, h, idx, weight, rel, d_table, d_wx, segs, seg_len)
-        return d_table, d_wx, None, None, None, None, None, None, None, dgamma, dbeta, dw3
+        return _returned(ctx, (d_table, d_wx), (dgamma, dbeta, dw3))
 
 
 def blend_mini_head_supported(backend, table, idx, segs):
@@ -770,28 +802,30 @@ class MiniTailFn(Function):
         backend = backend_for(c)
         c, small = c.contiguous(), small.contiguous()
         B, S, half, P = c.shape
-        H2, F = wl.shape[1], w4.shape[1]
+        H2 = wl.shape[1]
         rm, rv, momentum, eps = bufs
         y, part = mini_tail_first(backend, c, small, wl, G)
         coef1 = c.new_empty(S * H2, 4)
         backend.pw_stats_finalize(part, gamma1, beta1, rm, rv, momentum, eps, coef1)
         out, arg = mini_tail_second(backend, y, coef1, w4, G)
+        # two layers: W_l with the norm (the row bias ``small`` joins its output), W4 without one, pooled
+        # directly (no raw output).  W_l is half of a split: autograd's concatenation places its gradient.
+        chain = _chain_layout([Stack1dLayer(False, bufs), Stack1dLayer(False, None)])
         ctx.G = G
-        ctx.slots = _take_slots(ctx, 5, (gamma1, beta1, w4))
-        ctx.save_for_backward(c, y, coef1, arg, wl, gamma1, beta1, w4)
+        _save_chain(ctx, chain, (c, arg), (y.view(B * S, H2, P), None), (coef1, None), (wl, gamma1, beta1, w4),
+                    no_slot=(chain[0].iw,))
         ctx.mark_non_differentiable(arg)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        c, y, coef1, arg, wl, gamma1, beta1, w4 = ctx.saved_tensors
+        (c, arg), ys, coefs, lays = _saved_chain(ctx)
         backend = backend_for(c)
         B, S, half, P = c.shape
-        H2, F = wl.shape[1], w4.shape[1]
-        G = ctx.G
-        yf = y.view(B * S, H2, P)
-        dw4 = None
-        da = c.new_empty(B * S, H2, P)
+        G, top = ctx.G, lays[-1]
+        F, H2 = top.w.shape[1:]
+        grads = [None] * len(ctx.slots)
+        enter, dz, pending = len(lays) - 1, None, None
         if mini_tail_sparse_supported(backend, F, H2, G, P):
             # No norm and no ReLU between conv4 and the max: the gradient of its output is ONE non-zero
             # per (channel, group) -- kept as entries (value, position); the dense (B S, F, P) tensor
@@ -799,42 +833,27 @@ class MiniTailFn(Function):
             # dense launch's result), the weight gradient is a sparse product on the vector ALUs that
             # leaves the dense launch's partials (bit for bit its dW4, deferred reduction included).
             ent = backend.pool_tail_pack(dout.contiguous().view(B * S, F, P // G), arg.view(B * S, F, P // G))
-            if ctx.needs_input_grad[7]:
-                dw4 = _dst(ctx.slots[2], c, S, F, H2)
-                backend.pw_wgrad_sparse(ent, G, yf, dw4, ng=S, x_coef=coef1, final=ctx.slots[2] is not None)
-            part = backend.pw_dgrad_bn_reduce_sparse(ent, G, w4.transpose(1, 2), yf, coef1, da, ng=S)
+            if ctx.needs_input_grad[ctx.lead + top.iw]:
+                slot = ctx.slots[top.iw]
+                grads[top.iw] = _dst(slot, c, S, F, H2)
+                backend.pw_wgrad_sparse(ent, G, ys[0], grads[top.iw], ng=S, x_coef=coefs[0], final=slot is not None)
+            da = c.new_empty(B * S, H2, P)
+            part = backend.pw_dgrad_bn_reduce_sparse(ent, G, _transposed(top.w), ys[0], coefs[0], da, ng=S)
+            enter, pending = enter - 1, (da, part)      # the top layer is done: on with the norm backward below it
         else:
             # gradient of the last conv's output: the pooled gradient at the arg-max, zero elsewhere
             dz = c.new_empty(B, S, F, P // G, G)
             backend.group_max_pool_backward(dout.contiguous(), arg, dz)
-            dzf = dz.view(B * S, F, P)
-            if ctx.needs_input_grad[7]:
-                dw4 = _wgrad(backend, dzf, yf, coef1, ng=S, slot=ctx.slots[2])
-            part = backend.pw_dgrad_bn_reduce(dzf, w4.transpose(1, 2), yf, coef1, da, ng=S)
-        dgamma, dbeta = _dst(ctx.slots[0], c, S * H2), _dst(ctx.slots[1], c, S * H2)
-        cf = c.view(B * S, half, P)
-        dwl = None
-        if (FOLD_NORM_BWD and ctx.needs_input_grad[4] and G in (16, 64)
-                and backend.pw_wgrad_bn_supported(H2, half, P)):
-            # norm backward + row-bias gradient + weight gradient in one launch (dY over da)
-            dsmall = (c.new_zeros if G == 64 else c.new_empty)(B, S, H2, P // G)
-            dwl = c.new_empty(S, H2, half)
-            backend.pw_wgrad_bn_backward(da, yf, coef1, gamma1, part, cf, da, dwl, dgamma, dbeta, ng=S,
-                                         x_coef=None, d_row_bias=dsmall.view(B * S, H2, -1), group=G)
-            dyf = da
-        else:
-            dy = torch.empty_like(y)
-            dsmall = c.new_empty(B, S, H2, P // G)
-            backend.bn_relu_backward_apply(da.view(B, S * H2, P), y.view(B, S * H2, P), gamma1,
-                                           None, coef1, part, dy.view(B, S * H2, P), dgamma, dbeta,
-                                           d_row_bias=dsmall.view(B, S * H2, -1), group=G)
-            dyf = dy.view(B * S, H2, P)
-            if ctx.needs_input_grad[4]:
-                dwl = _wgrad(backend, dyf, cf, None, ng=S)
-        dc = torch.empty_like(c)
-        backend.pw_layer_forward(dyf, wl.transpose(1, 2), ng=S, y=dc.view(B * S, half, P))
-        setattr(dc, _OWNED_MARK, True)      # nobody else holds this gradient buffer
-        return dc, dsmall, None, None, dwl, dgamma, dbeta, dw4
+            dz = dz.view(B * S, F, P)
+
+        def input_grad(dy, lay, dsmall):
+            dc = torch.empty_like(c)
+            backend.pw_layer_forward(dy, _transposed(lay.w), ng=S, y=dc.view(B * S, half, P))
+            setattr(dc, _OWNED_MARK, True)      # nobody else holds this gradient buffer
+            return dc, dsmall.view(B, S, H2, -1)
+        inputs = _chain_backward(backend, ctx, lays, c.view(B * S, half, P), ys, coefs, grads, enter, dz, pending,
+                                 ng=S, input_grad=input_grad, rb_group=G)
+        return _returned(ctx, inputs, grads)
 
 
 # Tests flip this to obtain the dense backward of the MiniPointNet tail on the same inputs.
@@ -995,7 +1014,7 @@ class Stack1dFn(Function):
             grads[last.ig], grads[last.ibeta] = dgamma, dbeta
         else:
             dz = dout
-            if last.b is not None and need[3 + last.ib]:
+            if last.b is not None and need[ctx.lead + last.ib]:
                 # (one workgroup per channel in a fixed order: ATen's two-axis reduction took 13 - 18 us)
                 grads[last.ib] = backend.channel_sum(dz if S == 1 else dz.view(B, S * cl, P))
 
@@ -1010,7 +1029,7 @@ class Stack1dFn(Function):
             return dx
         dx = _chain_backward(backend, ctx, lays, x, ys, coefs, grads, len(lays) - 1, dz, ng=S, input_grad=input_grad)
         for lay in lays:
-            if lay.bn is not None and lay.b is not None and need[3 + lay.ib]:
+            if lay.bn is not None and lay.b is not None and need[ctx.lead + lay.ib]:
                 # the bias in front of a norm: gradient identically zero.
                 # With a slot in the flat gradient vector the answer is None: FlatTrainState.collect()
                 # zero-fills every parameter that got no gradient (one multi-tensor fill for all of
@@ -1018,7 +1037,7 @@ class Stack1dFn(Function):
                 # is overwritten in every step.  Without a flat state: a zero tensor, as ATen returns
                 # (a None would make a per-parameter optimiser skip the parameter).
                 grads[lay.ib] = None if slots[lay.ib] is not None else torch.zeros_like(lay.b)
-        return (dx, None, None) + tuple(grads)
+        return _returned(ctx, (dx,), grads)
 
 
 def stack1d_supported(backend, x, shapes, norms, S=1):

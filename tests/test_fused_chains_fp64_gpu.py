@@ -21,6 +21,8 @@ the restatement's own float32 error on the normalised pre-activations.  What eac
   per workgroup and per slot in another order than torch does.  ``BOUNDS`` lists the tensors that need
   more, each with the cause that can be read in the kernel (DESIGN.md, "chains against float64");
 * the bias in front of a norm: an exact zero tensor (None with a gradient slot);
+* a frozen parameter: no gradient at all; a gradient slot of the quality head's functions: bit for bit
+  what the same route returns without slots;
 * housekeeping: module switches and the injected back end restored, no weight-gradient reduction
   left pending.
 
@@ -222,11 +224,33 @@ def _small(backend, g, w_g, bias, S):
     return torch.matmul(w_g.unsqueeze(0), g) + bias.view(1, S, ref.H2, 1)
 
 
+# the parameters of the quality head's functions that have a gradient slot ('w', which W_g and W_l are
+# split from, is filled by autograd's concatenation)
+_SLOTTED = {'mini': ('gamma0', 'beta0', 'w3', 'gamma1', 'beta1', 'w4'), 'blend': ('gamma0', 'beta0', 'w3')}
+
+
+def _leaves(d, names, case, family, dev):
+    """-> ({name: leaf} with the case's frozen ones requiring no gradient, the owner of their slots | None)."""
+    t = {n: _leaf(d[n], dev, n not in case.get('frozen', ())) for n in names}
+    return t, _Owner([t[n] for n in _SLOTTED[family]]) if case.get('slots') else None
+
+
+def _gradients(t, case, family, owner):
+    """{name: gradient} of the leaves ``t``: the flat vector itself where there are slots; a frozen leaf has none."""
+    frozen = case.get('frozen', ())
+    assert all(t[n].grad is None for n in frozen)
+    grads = {n: v.grad for n, v in t.items() if n not in frozen}
+    if owner is not None:
+        owner.collect()
+        grads.update(zip(_SLOTTED[family], owner.views))
+    return grads
+
+
 def _run_mini(cfg, case, d, dev):
     from nesie_amd.kernels import injected_backend
     S, G = cfg['S'], cfg['G']
     names = ('c0', 'gamma0', 'beta0', 'w3', 'w', 'bias', 'gamma1', 'beta1', 'w4')
-    t = {n: _leaf(d[n], dev) for n in names}
+    t, owner = _leaves(d, names, case, 'mini', dev)
     bufs = [_bufs(d, 0, dev), _bufs(d, 1, dev)]
     part = ref.stat_partials(d['c0']).to(dev)
     c, g = fused_mlp.MiniHeadFn.apply(t['c0'], part, bufs[0], G, t['gamma0'], t['beta0'], t['w3'])
@@ -240,7 +264,7 @@ def _run_mini(cfg, case, d, dev):
         loss = loss + (c * d['g_c'].to(dev)).sum()
         outs['c'] = c.detach()
     loss.backward()
-    grads = {n: v.grad for n, v in t.items()}
+    grads = _gradients(t, case, 'mini', owner)
     grads['small'] = small.grad
     return outs, grads, [(b[0], b[1]) for b in bufs]
 
@@ -264,12 +288,12 @@ def _run_mini_eval(cfg, case, d, dev):
 def _run_blend(cfg, case, d, dev):
     S, G = cfg['S'], cfg['G']
     names = ('table', 'wx', 'gamma0', 'beta0', 'w3')
-    t = {n: _leaf(d[n], dev) for n in names}
+    t, owner = _leaves(d, names, case, 'blend', dev)
     bufs = [_bufs(d, 0, dev)]
     c, g = fused_mlp.BlendMiniHeadFn.apply(t['table'], t['wx'], d['idx'].to(dev), d['weight'].to(dev),
                                            d['rel'].to(dev), S, G, bufs[0], G, t['gamma0'], t['beta0'], t['w3'])
     ((c * d['g_c'].to(dev)).sum() + (g * d['g_g'].to(dev)).sum()).backward()
-    return {'c': c.detach(), 'g': g.detach()}, {n: v.grad for n, v in t.items()}, [(bufs[0][0], bufs[0][1])]
+    return {'c': c.detach(), 'g': g.detach()}, _gradients(t, case, 'blend', owner), [(bufs[0][0], bufs[0][1])]
 
 
 _RUN = {'sa': _run_sa, 'sa_eval': _run_sa_eval, 's1d': _run_s1d, 'mini': _run_mini, 'mini_eval': _run_mini_eval,
@@ -280,20 +304,33 @@ def _err(dev_t, want):
     return float((dev_t.detach().double().cpu() - want).abs().max())
 
 
-def check_case(name, case, dev):
-    """Run ``case`` and assert everything the module docstring lists; -> [(tensor, ratio)]."""
-    cfg = ref.DATA[case['data']]
-    family = cfg['family'] + ('' if cfg.get('training', True) else '_eval')
-    d, margin, r32, r64 = _reference(case['data'], bool(case.get('second_consumer')))
+def _run(family, cfg, case, d, dev):
+    """-> (outs, grads, stats, the back end) of ``case`` on its route."""
     try:
         with _route(case.get('answers', {}), case.get('switches', {}), case.get('atomic', False)) as backend:
-            outs, grads, stats = _RUN[family](cfg, case, d, dev)
+            result = _RUN[family](cfg, case, d, dev)
             torch.cuda.synchronize()
     finally:
         if HipKernels._deferred is not None:        # a case that failed inside its window
             HipKernels.begin_deferred_reductions()
             HipKernels._deferred = None
+    return (*result, backend)
+
+
+def check_case(name, case, dev):
+    """Run ``case`` and assert everything the module docstring lists; -> [(tensor, ratio)]."""
+    cfg = ref.DATA[case['data']]
+    family = cfg['family'] + ('' if cfg.get('training', True) else '_eval')
+    d, margin, r32, r64 = _reference(case['data'], bool(case.get('second_consumer')))
+    outs, grads, stats, backend = _run(family, cfg, case, d, dev)
     launched = backend.launched
+    if case.get('slots') and family in _SLOTTED:
+        # a slot holds exactly what the same route returns without slots
+        plain = _run(family, cfg, dict(case, slots=False), d, dev)[1]
+        for k in _SLOTTED[family]:
+            same = torch.equal(grads[k].reshape(plain[k].shape), plain[k])
+            print(f'SLOT {name} {k} equals the unslotted gradient bit for bit: {same}')
+            assert same, f'{name}: the slot of {k} differs from the unslotted gradient'
     # route
     for m in case.get('present', ()):
         assert m in launched, f'{name}: {m} was not launched: {launched}'
@@ -335,9 +372,9 @@ def check_case(name, case, dev):
         # every gradient of the reference is compared, but: the input's where the case asks for none, an
         # identically zero one that a slot leaves to the zero fill, a frozen parameter's
         skip = set() if case.get('x_grad', cfg['family'] != 'sa') else {'x'}
-        if case.get('frozen'):
-            sa_names = [f'{k}{l}' for l in range(len(cfg['chans']) - 1) for k in ('w', 'gamma', 'beta')]
-            skip |= {sa_names[i] for i in case['frozen']}
+        if case.get('frozen'):      # (a set-abstraction case names them by position, the others by name)
+            sa_names = [f'{k}{l}' for l in range(len(cfg.get('chans', ())) - 1) for k in ('w', 'gamma', 'beta')]
+            skip |= {i if isinstance(i, str) else sa_names[i] for i in case['frozen']}
         missing = [k for k in r64.grads if k not in grads and k not in skip and r64.grads[k].any()
                    and not (k == 'x' and 'x[3:]' in grads)]
         assert not missing, f'{name}: gradients not compared: {missing}'
@@ -453,6 +490,16 @@ MINI_CASES = {
     'mini_s2_g16_unfolded': dict(data='mini_s2_g16', **_UNFOLDED),
     'mini_s1_g64_unfolded': dict(data='mini_s1_g64', **_UNFOLDED),
     'mini_s2_g16_unmarked_dc': dict(data='mini_s2_g16', second_consumer=True, present=('group_max_pool_backward_add',)),
+    'mini_s2_g16_slots': dict(data='mini_s2_g16', slots=True, **_SPARSE),
+    'mini_s1_g64_dense_slots': dict(data='mini_s1_g64', slots=True, **_DENSE),
+    # W_l (the whole weight it is split from) without a gradient: the norm backward as its own apply pass
+    'mini_s2_g16_frozen_wl': dict(data='mini_s2_g16', frozen=('w',), present=('pool_tail_pack', 'pw_wgrad_sparse'),
+                                  absent=('pw_wgrad_bn_backward',), count={'bn_relu_backward_apply': 2}),
+    'mini_s1_g64_frozen_w4': dict(data='mini_s1_g64', frozen=('w4',),
+                                  present=('pool_tail_pack', 'pw_dgrad_bn_reduce_sparse', 'pw_wgrad_bn_backward'),
+                                  absent=('pw_wgrad_sparse', 'group_max_pool_backward')),
+    'mini_s2_g16_frozen_w3': dict(data='mini_s2_g16', frozen=('w3',), **dict(_SPARSE, absent=('group_max_pool_backward',
+                                                                                              'pw_wgrad'))),
     'mini_eval_s2_g16': dict(data='mini_eval_s2_g16', present=('pw_layer_forward', 'pw_pool_finish')),
     'mini_eval_s1_g64': dict(data='mini_eval_s1_g64', present=('pw_layer_forward', 'pw_pool_finish')),
 }
@@ -473,6 +520,8 @@ BLEND_CASES = {
                                present=('blend_conv_backward', 'pw_bnb_coef')),
     # ... and the form itself (float atomics into that table), with the deterministic backward switched off
     'blend_atomic_form': dict(data='blend', atomic=True, present=('blend_conv_backward', 'pw_bnb_coef')),
+    'blend_slots': dict(data='blend', slots=True, present=('blend_conv_backward', 'pw_bnb_coef'),
+                        absent=('bn_relu_backward_apply',)),
 }
 
 

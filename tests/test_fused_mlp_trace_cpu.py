@@ -6,8 +6,10 @@ end, the autograd functions run end to end on CPU tensors, and the log of every 
 slip in the bookkeeping of a chain -- a gradient in the wrong position, a kernel reading the wrong
 saved tensor, a slot not written -- shows here and not only as a wrong number on the device.
 
-The fixture is this project's own record: ``python -m tests.test_fused_mlp_trace_cpu`` rewrites it
-from the code as it stands (only for a change that is MEANT to alter the launches)."""
+The fixture is this project's own record: ``python -m tests.test_fused_mlp_trace_cpu`` adds the cases
+it does not hold yet from the code as it stands -- record a new case BEFORE changing the code it is to
+hold -- and ``... CASE [CASE ...]`` records the named ones again (only for a change that is MEANT to
+alter their launches)."""
 import json
 import os
 
@@ -96,37 +98,49 @@ def _stack1d(S, c0, spec, x_grad=True, P=128, owner=False, sliced=False):
 H0, HALF, H2, F = 64, 32, 256, 128
 
 
-def _mini_tail(c, g, S, G):
+def _mini_tail(c, g, S, G, w, gamma1, beta1, w4):
     """side_pooling.fused_mini_pointnets behind the head: the per-proposal term through a one-layer
     ``Stack1dFn``, then ``MiniTailFn``."""
     K = g.shape[-1]
-    w = _leaf(S, H2, 2 * HALF)
     w_g, w_l = w.split(HALF, dim=2)
     small = fused_mlp.Stack1dFn.apply(g.reshape(B * S, HALF, K), (fused_mlp.Stack1dLayer(True, None),), S,
                                       w_g, _leaf(S * H2)).view(B, S, H2, K)
-    return fused_mlp.MiniTailFn.apply(c, small, _norm_bufs(S * H2), G, w_l, _leaf(S * H2), _leaf(S * H2),
-                                      _leaf(S, F, H2))
+    return fused_mlp.MiniTailFn.apply(c, small, _norm_bufs(S * H2), G, w_l, gamma1, beta1, w4)
 
 
-def _mini(S, G, second_consumer=False):
+# where the parameters sit in the tuples that the three backwards return
+_HEAD_AT = {'MiniHeadFn': 4, 'BlendMiniHeadFn': 9}         # gamma0, beta0, w3 from there on
+_TAIL_AT = 5                                                # gamma1, beta1, w4 (W_l, in front, has no slot)
+
+
+def _mini(S, G, second_consumer=False, owner=False, frozen=()):
+    """``frozen``: which of 'w' (the weight that W_g and W_l are split from), 'w3', 'w4' need no gradient."""
     P = 64 if G == 16 else 128
     c0 = _leaf(B, S, H0, P)
-    c, g = fused_mlp.MiniHeadFn.apply(c0, torch.zeros(S * H0, 2, 2), _norm_bufs(S * H0), G, _leaf(S * H0),
-                                      _leaf(S * H0), _leaf(S, HALF, H0))
-    loss = _mini_tail(c, g, S, G).sum()
+    head = [_leaf(S * H0), _leaf(S * H0), _leaf(S, HALF, H0, grad='w3' not in frozen)]
+    w = _leaf(S, H2, 2 * HALF, grad='w' not in frozen)
+    tail = [_leaf(S * H2), _leaf(S * H2), _leaf(S, F, H2, grad='w4' not in frozen)]
+    state = _Owner(head + tail) if owner else None
+    c, g = fused_mlp.MiniHeadFn.apply(c0, torch.zeros(S * H0, 2, 2), _norm_bufs(S * H0), G, *head)
+    loss = _mini_tail(c, g, S, G, w, *tail).sum()
     if second_consumer:     # autograd sums the two gradients of c into a tensor of its own: no mark on it
         loss = loss + c.sum()
     loss.backward()
-    return []
+    if not owner:
+        return []
+    at = [('MiniHeadFn', _HEAD_AT['MiniHeadFn'] + j) for j in range(3)] + [('MiniTailFn', _TAIL_AT + j) for j in range(3)]
+    return [(f, i, v) for (f, i), v in zip(at, state.views)]
 
 
-def _blend(S=2, G=16, P=64, m=16):
+def _blend(S=2, G=16, P=64, m=16, owner=False):
     n = S * P
+    head = [_leaf(S * H0), _leaf(S * H0), _leaf(S, HALF, H0)]
+    state = _Owner(head) if owner else None
     c, g = fused_mlp.BlendMiniHeadFn.apply(
         _leaf(B, m, S * H0), _leaf(S, H0, 3), torch.zeros(B, n, 3, dtype=torch.int32), torch.zeros(B, n, 3),
-        torch.zeros(B, n, 3), S, P, _norm_bufs(S * H0), G, _leaf(S * H0), _leaf(S * H0), _leaf(S, HALF, H0))
+        torch.zeros(B, n, 3), S, P, _norm_bufs(S * H0), G, *head)
     (c.sum() + g.sum()).backward()
-    return []
+    return [('BlendMiniHeadFn', _HEAD_AT['BlendMiniHeadFn'] + j, v) for j, v in enumerate(state.views)] if owner else []
 
 
 def _sa_modules(chans):
@@ -237,6 +251,11 @@ CASES = {
     'mini_s2_g16_unfolded': (_mini, dict(S=2, G=16), {'pw_wgrad_bn_supported': False}, {}),
     'mini_s1_g64_unfolded': (_mini, dict(S=1, G=64), {'pw_wgrad_bn_supported': False}, {}),
     'mini_s2_g16_unmarked_dc': (_mini, dict(S=2, G=16, second_consumer=True), {}, {}),
+    'mini_s2_g16_slots': (_mini, dict(S=2, G=16, owner=True), {}, {}),
+    'mini_s1_g64_dense_slots': (_mini, dict(S=1, G=64, owner=True), {}, {'MINI_TAIL_SPARSE': False}),
+    'mini_s2_g16_frozen_wl': (_mini, dict(S=2, G=16, frozen=('w',)), {}, {}),
+    'mini_s1_g64_frozen_w4': (_mini, dict(S=1, G=64, frozen=('w4',)), {}, {}),
+    'mini_s2_g16_frozen_w3': (_mini, dict(S=2, G=16, frozen=('w3',)), {}, {}),
     'sa_eval': (_sa_eval, dict(chans=SA2, ns=32), {}, {}),
     'sa_eval_ns16': (_sa_eval, dict(chans=(4, 64, 128), ns=16), {}, {}),
     'mini_eval_s2_g16': (_mini_eval, dict(S=2, G=16), {}, {}),
@@ -244,6 +263,7 @@ CASES = {
     'blend_folded': (_blend, {}, {}, {}),
     'blend_unfolded': (_blend, {}, {}, {'FOLD_NORM_BWD': False}),
     'blend_atomic_table': (_blend, {}, {'blend_backward_writes_table': False}, {}),
+    'blend_slots': (_blend, dict(owner=True), {}, {}),
 }
 
 
@@ -301,14 +321,20 @@ def test_launch_trace_equals_the_record(name, recorded):
         assert grad.untyped_storage()._cdata == slot.untyped_storage()._cdata
 
 
-def write_fixture():
+def write_fixture(names=None):
+    """Record ``names`` (default: the cases the fixture does not hold yet); every other entry is written
+    back as it was read."""
+    with open(FIXTURE) as fh:
+        held = json.load(fh)
     lines = []
     for name in sorted(CASES):
-        entries = ',\n'.join('  ' + json.dumps(e, separators=(',', ':')) for e in run_case(name)[0])
+        log = run_case(name)[0] if name not in held or name in (names or ()) else held[name]
+        entries = ',\n'.join('  ' + json.dumps(e, separators=(',', ':')) for e in log)
         lines.append(f'{json.dumps(name)}: [\n{entries}\n]')
     with open(FIXTURE, 'w') as fh:
         fh.write('{\n' + ',\n'.join(lines) + '\n}\n')
 
 
 if __name__ == '__main__':
-    write_fixture()
+    import sys
+    write_fixture(sys.argv[1:])
