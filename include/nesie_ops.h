@@ -931,6 +931,88 @@ int nesie_conv_wgrad_bn(int b, int cout, int cin, long long p, const float *da, 
                         const float *x_coef, int x_relu, float *dw, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* mmdet3d/ops/voxel: dynamic / hard voxelization (src/voxelization_cpu.cpp, voxelization_cuda.cu)
+ * and dynamic_scatter (src/scatter_points_cuda.cu).  fp32 features, int32 coordinates, 3 spatial
+ * dimensions.  The default training step launches none of it.
+ * Grid (voxelization_cuda.cu:209-211): grid[j] = roundf((hi[j] - lo[j]) / vs[j]) for j = x, y, z,
+ *   computed on the host in fp32, halves rounded away from zero.  voxel_size (3 floats, x y z) and
+ *   coors_range (6 floats, lo xyz then hi xyz) are HOST pointers.  Every grid[j] >= 1 and
+ *   cells = grid_x * grid_y * grid_z < 2^31, else NESIE_ERR_UNSUPPORTED before any launch;
+ *   nesie_voxel_grid_size is the size query: grid[3] (x, y, z) and *cells, or that status.
+ * Cell of a point (voxelization_cpu.cpp:20-37, voxelization_cuda.cu:33-60), all fp32:
+ *   c_j = floor((p_j - lo_j) / vs_j), one subtraction, one IEEE division, then floor.  The point is
+ *   out of range if any c_j < 0, any c_j >= grid_j, or a quotient is NaN or infinite (a quotient of
+ *   2^31 or more is out of range too).  Coordinates are written reversed, (c_z, c_y, c_x).  An
+ *   out-of-range point gets (-1, -1, -1).  DEPARTURE 1: that is the row of the reference's CPU
+ *   program; its CUDA kernel returns at the first failing axis and leaves (-1, 0, 0) or
+ *   (-1, -1, 0).  points[N, C], C >= 3; columns beyond the first three are payload.
+ * nesie_dynamic_voxelize: coors[N,3] i32, WRITTEN in full.
+ * nesie_hard_voxelize (voxelization_cpu.cpp:65-96, the same result as voxelization_cuda.cu:106-180):
+ *   walk the points in ascending index; a cell becomes a voxel the first time one of its points is
+ *   met, provided fewer than max_voxels voxels exist, otherwise that point and every later point of
+ *   the cell are dropped; a point of an existing voxel is stored at slot num if num < max_points,
+ *   else dropped.  So voxels appear in order of first appearance, a voxel's points are in ascending
+ *   index, num_points_per_voxel = min(count, max_points), *voxel_num = min(distinct in-range
+ *   cells, max_voxels).  voxels[max_voxels, max_points, C] f32, coors[max_voxels, 3] i32,
+ *   num_points_per_voxel[max_voxels] i32, voxel_num one i32 ON THE DEVICE (the entry never
+ *   synchronises).  The rows below *voxel_num are WRITTEN in full, unused slots 0; the rows at and
+ *   above it are NOT TOUCHED and keep whatever the caller's buffers held.  max_points, max_voxels
+ *   >= 1 (the reference's -1 means dynamic voxelization: call that entry).
+ * nesie_dynamic_scatter_forward (scatter_points_cuda.cu:183-234): coors[N,3] i32; dims[3] (HOST
+ *   pointer) are exclusive upper bounds of the three columns, each >= 1, product < 2^31, else
+ *   NESIE_ERR_UNSUPPORTED.  A row is invalid if any entry is negative or >= its dims entry (the
+ *   reference knows negative entries only; it has no bound to test against).  The voxels are the
+ *   distinct valid rows in ascending lexicographic order (the order of at::unique_dim).
+ *   coors_map[N] = each point's voxel row, -1 for an invalid row; voxel_coors[M,3];
+ *   reduce_count[M] = points per voxel; voxel_feats[M,C]: reduce_type 2 (max) per voxel and channel
+ *   over its points in ascending point index starting from -inf, a value replacing the running one
+ *   only if it compares greater -- fmaxf's value: a NaN never wins (of +0 and -0 the first met
+ *   stays); 0 (sum) an fp32 running sum in ASCENDING POINT INDEX without contraction; 1 (mean)
+ *   that sum divided by (float)count, IEEE division.  No float atomics: bitwise reproducible.
+ *   DEPARTURE 2: the reference always discards the first row of unique_dim's output on the
+ *   assumption that it is (-1, -1, -1), and so loses the smallest real voxel when no row is
+ *   invalid; here a voxel is dropped only if it is the invalid one.
+ *   M is data dependent: the caller allocates voxel_feats, voxel_coors, reduce_count with N rows;
+ *   *num_voxels = M is one i32 on the device and only the first M rows are written.  Two arrays
+ *   are saved for the backward: order[N], the point indices sorted by (voxel, index), invalid
+ *   rows last, and voxel_start[N], of which the first M entries hold the position in `order` where
+ *   each voxel's points begin.  voxel_start is the one argument added to the proposed list: the
+ *   max backward walks a voxel's points in index order and has to know where they begin.
+ * nesie_dynamic_scatter_backward (:236-303): grad_feats[N,C] WRITTEN in full, zeros for invalid
+ *   rows.  sum: grad_voxel[map]; mean: grad_voxel[map] / (float)count, IEEE division; max: per
+ *   voxel and channel the LOWEST-INDEX point whose feature equals voxel_feats takes the gradient
+ *   (:136-160, the atomicMin of the index), every other point gets 0.  A cell whose maximum no
+ *   feature equals (every feature NaN) passes no gradient; the reference writes out of bounds
+ *   there (its reduce_from keeps the fill value num_input).  feats, voxel_feats, order,
+ *   voxel_start and num_voxels are read by the max backward only and may be null otherwise.
+ * Scratch: `workspace` holds nesie_voxel_workspace_bytes(n, cells) bytes (cells = the grid's, or
+ *   the product of dims) and may be reused by the next call on the same stream.  No entry
+ *   allocates or synchronises; every launch (and the 4-byte memset of an empty call) goes on the
+ *   given stream, so forward and backward capture into a graph.
+ * A negative size, reduce_type outside 0 .. 2, max_points / max_voxels < 1, C < 3 for the
+ *   voxelizers, or a null pointer for a non-empty problem is NESIE_ERR_INVALID_ARG; more than
+ *   2^31 - 1025 points NESIE_ERR_UNSUPPORTED.  N == 0 or C == 0 succeeds without a kernel launch
+ *   and sets *voxel_num / *num_voxels to 0 (:192-196). */
+int nesie_voxel_grid_size(const float *voxel_size, const float *coors_range, int *grid,
+                          long long *cells);
+int nesie_voxel_workspace_bytes(long long n, long long cells, long long *out);
+int nesie_dynamic_voxelize(long long n, int c, const float *points, const float *voxel_size,
+                           const float *coors_range, int *coors, void *stream);
+int nesie_hard_voxelize(long long n, int c, const float *points, const float *voxel_size,
+                        const float *coors_range, int max_points, int max_voxels, float *voxels,
+                        int *coors, int *num_points_per_voxel, int *voxel_num, void *workspace,
+                        void *stream);
+int nesie_dynamic_scatter_forward(long long n, int c, const float *feats, const int *coors,
+                                  const int *dims, int reduce_type, float *voxel_feats,
+                                  int *voxel_coors, int *coors_map, int *reduce_count,
+                                  int *num_voxels, int *order, int *voxel_start, void *workspace,
+                                  void *stream);
+int nesie_dynamic_scatter_backward(long long n, int c, const float *grad_voxel, const float *feats,
+                                   const float *voxel_feats, const int *coors_map,
+                                   const int *reduce_count, const int *order,
+                                   const int *voxel_start, const int *num_voxels, int reduce_type,
+                                   float *grad_feats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -682,6 +682,105 @@ class HipKernels:
         _launch("nesie_roiaware_pool3d_backward", grad_out, n, p, ox, oy, oz, c, m,
                 pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in, int(pool_method))
 
+    @staticmethod
+    def voxel_grid_size(voxel_size, coors_range):
+        """-> ((grid_x, grid_y, grid_z), cells) of a voxel grid, ``roundf((hi - lo) / vs)`` in fp32;
+        raises on a grid the kernels refuse (nesie_voxel_grid_size)."""
+        vs = (ctypes.c_float * 3)(*voxel_size)
+        cr = (ctypes.c_float * 6)(*coors_range)
+        grid, cells = (ctypes.c_int * 3)(), ctypes.c_longlong()
+        _lib.call("nesie_voxel_grid_size", ctypes.addressof(vs), ctypes.addressof(cr),
+                  ctypes.addressof(grid), ctypes.addressof(cells))
+        return tuple(grid), cells.value
+
+    @staticmethod
+    def voxel_workspace_bytes(n, cells):
+        """Scratch bytes of the sorted voxel ops for n points over ``cells`` cells; raises on sizes
+        the kernels refuse (nesie_voxel_workspace_bytes)."""
+        out = ctypes.c_longlong()
+        _lib.call("nesie_voxel_workspace_bytes", n, cells, ctypes.addressof(out))
+        return out.value
+
+    def dynamic_voxelize(self, points, voxel_size, coors_range, coors):
+        """points (N,C>=3) -> coors (N,3) i32, (z, y, x) cell or (-1, -1, -1); written in full."""
+        _check(points, coors); _f32(points); _i32(coors)
+        n, c = points.shape
+        assert tuple(coors.shape) == (n, 3)
+        vs = (ctypes.c_float * 3)(*voxel_size)
+        cr = (ctypes.c_float * 6)(*coors_range)
+        _launch("nesie_dynamic_voxelize", points, n, c, points, ctypes.addressof(vs),
+                ctypes.addressof(cr), coors)
+
+    def hard_voxelize(self, points, voxel_size, coors_range, voxels, coors, num_points_per_voxel,
+                      voxel_num, workspace=None):
+        """points (N,C>=3) -> voxels (max_voxels, max_points, C), coors (max_voxels, 3),
+        num_points_per_voxel (max_voxels) and voxel_num (1) i32 on the device; only the rows below
+        voxel_num are written (nesie_hard_voxelize).  ``workspace`` (uint8, at least
+        ``voxel_workspace_bytes``) is allocated when not given."""
+        _check(points, voxels, coors, num_points_per_voxel, voxel_num); _f32(points, voxels)
+        _i32(coors, num_points_per_voxel, voxel_num)
+        n, c = points.shape
+        max_voxels, max_points = int(voxels.shape[0]), int(voxels.shape[1])
+        assert tuple(voxels.shape) == (max_voxels, max_points, c)
+        assert tuple(coors.shape) == (max_voxels, 3)
+        assert tuple(num_points_per_voxel.shape) == (max_voxels,) and voxel_num.numel() == 1
+        _, cells = self.voxel_grid_size(voxel_size, coors_range)
+        need = self.voxel_workspace_bytes(n, cells)
+        workspace = self._voxel_workspace(workspace, need, points.device)
+        vs = (ctypes.c_float * 3)(*voxel_size)
+        cr = (ctypes.c_float * 6)(*coors_range)
+        _launch("nesie_hard_voxelize", points, n, c, points, ctypes.addressof(vs),
+                ctypes.addressof(cr), max_points, max_voxels, voxels, coors, num_points_per_voxel,
+                voxel_num, workspace)
+
+    @staticmethod
+    def _voxel_workspace(workspace, need, device):
+        if workspace is None:
+            return _workspace(need, device)
+        _check(workspace)
+        if workspace.dtype != torch.uint8 or workspace.numel() < need:
+            raise ValueError(f"workspace must be uint8 with at least {need} bytes")
+        return workspace
+
+    def dynamic_scatter_forward(self, feats, coors, dims, reduce_type, voxel_feats, voxel_coors,
+                                coors_map, reduce_count, num_voxels, order, voxel_start,
+                                workspace=None):
+        """feats (N,C), coors (N,3) i32, dims 3 exclusive upper bounds, reduce_type 0 sum / 1 mean /
+        2 max -> voxel_feats (N,C), voxel_coors (N,3), reduce_count (N) of which the first
+        num_voxels (1, on the device) rows are written, coors_map (N) written in full, and order
+        (N), voxel_start (N) for the backward (nesie_dynamic_scatter_forward)."""
+        _check(feats, coors, voxel_feats, voxel_coors, coors_map, reduce_count, num_voxels, order,
+               voxel_start)
+        _f32(feats, voxel_feats)
+        _i32(coors, voxel_coors, coors_map, reduce_count, num_voxels, order, voxel_start)
+        n, c = feats.shape
+        assert tuple(coors.shape) == (n, 3) and tuple(voxel_feats.shape) == (n, c)
+        assert tuple(voxel_coors.shape) == (n, 3) and num_voxels.numel() == 1
+        assert coors_map.numel() == reduce_count.numel() == order.numel() == n
+        assert voxel_start.numel() == n and reduce_type in (0, 1, 2)
+        d = (ctypes.c_int * 3)(*(int(x) for x in dims))
+        cells = d[0] * d[1] * d[2] if min(d) >= 1 else 0
+        need = self.voxel_workspace_bytes(n, cells)
+        workspace = self._voxel_workspace(workspace, need, feats.device)
+        _launch("nesie_dynamic_scatter_forward", feats, n, c, feats, coors, ctypes.addressof(d),
+                int(reduce_type), voxel_feats, voxel_coors, coors_map, reduce_count, num_voxels,
+                order, voxel_start, workspace)
+
+    def dynamic_scatter_backward(self, grad_voxel, feats, voxel_feats, coors_map, reduce_count,
+                                 order, voxel_start, num_voxels, reduce_type, grad_feats):
+        """grad_voxel (>=M, C) -> grad_feats (N,C), written in full; a gather, no float atomics
+        (nesie_dynamic_scatter_backward)."""
+        _check(grad_voxel, feats, voxel_feats, coors_map, reduce_count, order, voxel_start,
+               num_voxels, grad_feats)
+        _f32(grad_voxel, feats, voxel_feats, grad_feats)
+        _i32(coors_map, reduce_count, order, voxel_start, num_voxels)
+        n, c = grad_feats.shape
+        assert tuple(feats.shape) == (n, c) and coors_map.numel() == n and order.numel() == n
+        assert grad_voxel.dim() == 2 and grad_voxel.shape[1] == c and reduce_type in (0, 1, 2)
+        _launch("nesie_dynamic_scatter_backward", grad_feats, n, c, grad_voxel, feats, voxel_feats,
+                coors_map, reduce_count, order, voxel_start, num_voxels, int(reduce_type),
+                grad_feats)
+
     def vote_targets(self, points, gt_boxes, gt_count):
         """points (B,N,C>=3), depth-frame gt_boxes (B,T,7), gt_count (B) int64 -> vote targets
         (B,N,9) and masks (B,N) int64 of get_targets_single, one launch."""
