@@ -1013,6 +1013,78 @@ int nesie_dynamic_scatter_backward(long long n, int c, const float *grad_voxel, 
                                    const int *voxel_start, const int *num_voxels, int reduce_type,
                                    float *grad_feats, void *stream);
 
+/* mmdet3d/ops/spconv: sparse 3-D convolution (semantics of ops/spconv/include/spconv/geometry.h
+ * :25-85 and spconv_ops.h:60-140; none of its structure).  fp32 features, int32 sites, 3 spatial
+ * dimensions, dilation 1, groups 1.  The default training step launches none of it.
+ * Sites and keys: a row of indices[N,4] is (b, z, y, x); the grid is spatial_shape = (D, H, W) with
+ *   batch_size samples; the key of a site is ((b * D + z) * H + y) * W + x.  batch_size * D * H * W
+ *   must be below 2^31 for the input AND the output grid, else NESIE_ERR_UNSUPPORTED (a
+ *   41 x 1600 x 1408 grid fits up to batch 23).  spatial_shape, ksize, stride, padding are HOST
+ *   pointers to 3 ints (z, y, x); at most 512 taps; N * K at most 2^31 - 1025 (the sort's limit).
+ * Geometry: cross-correlation.  Tap k enumerates (kz, ky, kx) row-major, weight is
+ *   [kz, ky, kx, Cin, Cout].  Output site o reads input site o * stride - padding + k per axis;
+ *   output size per axis (in + 2 * pad - (k - 1) - 1) / stride + 1 (nesie_spconv_out_shape is the
+ *   size query, an addition to the proposed list: the host needs the output grid before it sizes
+ *   out_indices).  Submanifold (subm != 0): stride 1 and padding k / 2 WHATEVER was passed
+ *   (spconv_ops.h:76-79), the output sites are the input sites.
+ * Rulebook = two gather tables and a count, functions of the indices alone (bit-identical from
+ *   build to build): nbr[M,K] = the input row that output row o reads at tap k, or -1;
+ *   nbr_t[N,K] = the output row that input row i feeds at tap k, or -1 (unique: (i, k) fixes the
+ *   output site); pair_num[K] = the valid entries of column k.  The output rows of a regular conv
+ *   are the distinct reachable output sites in ascending key order (= lexicographic (b, z, y, x));
+ *   of a submanifold conv the input rows themselves, same order (out_indices is then neither read
+ *   nor written by phase 1 and may be null; phase 2 takes the input indices as out_indices).
+ * Input validity: rows must lie inside the grid (b in 0 .. batch_size - 1) and be pairwise
+ *   distinct.  Offending rows -- a row outside the grid (tested per axis BEFORE a key is formed), and
+ *   every row of a run of equal keys except the one of lowest index -- are counted on the device and
+ *   take part in no pair.
+ * nesie_spconv_out_sites (phase 1): sorted_keys[N] / sorted_rows[N] = the input keys in ascending
+ *   order (an outside row carries the key batch_size * D * H * W and sorts last) and the rows that
+ *   own them; nbr_t[N,K] WRITTEN in full; out_indices[cap,4] with cap = min(N * K, output cells),
+ *   rows below M written; counts[2] on the device = {M, offending rows} (the entry never
+ *   synchronises; the caller reads both in one copy).
+ * nesie_spconv_gather_table (phase 2, M known): nbr[M,K] WRITTEN in full, pair_num[K].
+ * nesie_spconv_gather_gemm: dst[r] = sum_k src[table[r,k]] . W[k] for r < rows, taps ascending,
+ *   source channels ascending inside a tap, -1 (or an entry >= src_rows) a zero row.  W[k] is
+ *   [c_src, c_dst], or with weight_transposed != 0 it is stored [c_dst, c_src] and read transposed.
+ *   One accumulator chain (v_mfma_f32_32x32x2_f32, an fp32 fma chain) per output element: no float
+ *   atomics, no split over workgroups, no dependence on nesie_set_cu_count; dst WRITTEN in full.
+ *   Non-finite weights are outside the contract (a zero row times inf).  The four feature products
+ *   are this one entry: forward (nbr, W); input gradient dIn[i] = sum_k dOut[nbr_t[i,k]] . W[k]^T
+ *   (nbr_t, transposed); inverse-conv forward out'[i] = sum_k in'[nbr_t[i,k]] . W'[k] (nbr_t, W');
+ *   inverse-conv input gradient (nbr, transposed).  Any c_src, c_dst >= 1.
+ * nesie_spconv_wgrad: dW[k] = sum_r src[table[r,k]]^T . dout[r], r < rows.  The rows are cut into
+ *   min(16, ceil(rows / 512)) chunks (a function of `rows` only); every (tap, chunk) writes a
+ *   partial product into `workspace` (nesie_spconv_wgrad_workspace_bytes), a second launch adds the
+ *   partials in ascending chunk order.  dw[K, c_in, c_out] WRITTEN in full; bit-identical from run
+ *   to run.
+ * Scratch of phase 1: nesie_spconv_rules_workspace_bytes(n, kvol, subm).  No entry allocates or
+ *   synchronises; every launch and memset goes on the given stream.
+ * n == 0 (phase 1), m == 0 (phase 2), rows == 0 (and, for wgrad, src_rows == 0) succeed without
+ *   touching the device.  A negative size, a size triple with an entry < 1 (padding < 0), or a null
+ *   pointer for a non-empty problem is NESIE_ERR_INVALID_ARG. */
+int nesie_spconv_rules_workspace_bytes(long long n, int kvol, int subm, long long *out);
+int nesie_spconv_out_shape(const int *spatial_shape, const int *ksize, const int *stride,
+                           const int *padding, int subm, int batch_size, int *out_shape,
+                           long long *out_cells);
+int nesie_spconv_out_sites(long long n, const int *indices, int batch_size,
+                           const int *spatial_shape, const int *ksize, const int *stride,
+                           const int *padding, int subm, int *sorted_keys, int *sorted_rows,
+                           int *nbr_t, int *out_indices, int *counts, void *workspace,
+                           void *stream);
+int nesie_spconv_gather_table(long long m, const int *out_indices, long long n,
+                              const int *sorted_keys, const int *sorted_rows, int batch_size,
+                              const int *spatial_shape, const int *ksize, const int *stride,
+                              const int *padding, int subm, int *nbr, int *pair_num, void *stream);
+int nesie_spconv_gather_gemm(long long rows, long long src_rows, int kvol, int c_src, int c_dst,
+                             const float *src, const float *weight, int weight_transposed,
+                             const int *table, float *dst, void *stream);
+int nesie_spconv_wgrad_workspace_bytes(long long rows, int kvol, int c_in, int c_out,
+                                       long long *out);
+int nesie_spconv_wgrad(long long rows, long long src_rows, int kvol, int c_in, int c_out,
+                       const float *src, const float *dout, const int *table, float *dw,
+                       void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,14 +39,13 @@
 #include <math.h>
 
 #include "common.h"
+#include "voxel_sort.h"
 
 namespace nesie {
 
 constexpr int VX_BLOCK = 256;
-constexpr int VX_SORT_TILE = 1024;  // keys per sort workgroup: 4 waves x 4 rounds x 64 lanes
 constexpr int VX_SCAN_TILE = 1024;  // ints per scan workgroup: 256 threads x 4
 constexpr int VX_CT = 256;          // channels one reduce pass holds (4 per lane)
-constexpr long long VX_MAX_N = 2147483647LL - VX_SORT_TILE;
 
 struct VxGrid {
   float lo[3], vs[3];
@@ -448,13 +447,7 @@ __global__ __launch_bounds__(VX_BLOCK) void vx_backward_max_kernel(
 // ---- host side
 static long long vx_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 
-struct VxWorkspace {
-  unsigned *ka, *kb;
-  int *ia, *ib, *flag, *hist, *sums, *meta;
-  long long nb, ints;
-};
-
-static VxWorkspace vx_carve(void *ws, long long n) {
+VxWorkspace vx_carve(void *ws, long long n) {
   VxWorkspace w;
   w.nb = vx_cdiv(n, VX_SORT_TILE);
   const long long hist = 256 * w.nb;
@@ -472,7 +465,7 @@ static VxWorkspace vx_carve(void *ws, long long n) {
   return w;
 }
 
-static int vx_check_n_cells(const char *W, long long n, long long cells) {
+int vx_check_n_cells(const char *W, long long n, long long cells) {
   NESIE_REQUIRE(n >= 0, W);
   if (cells < 1 || cells >= 2147483648LL) {
     set_error("%s: %lld cells outside 1 .. 2^31 - 1", W, cells);
@@ -517,8 +510,8 @@ static int vx_grid(const char *W, const float *voxel_size, const float *coors_ra
   } while (0)
 
 // out may alias in.  total_out / capped: see vx_scan_sums_kernel
-static int vx_scan(const char *W, long long n, const int *in, int *out, int *sums, int *total_out,
-                   int *capped, int cap, hipStream_t s) {
+int vx_scan(const char *W, long long n, const int *in, int *out, int *sums, int *total_out,
+            int *capped, int cap, hipStream_t s) {
   const long long nt = vx_cdiv(n, VX_SCAN_TILE);
   hipLaunchKernelGGL(vx_scan_tiles_kernel, dim3((unsigned)nt), dim3(VX_BLOCK), 0, s, n, in, out,
                      sums);
@@ -541,8 +534,8 @@ static int vx_passes(long long cells) {  // keys lie in 0 .. cells
 
 // sorts (w.ka, w.ia) by key; the sorted keys end in *keys, the indices in *idx (`last_idx` when
 // given receives the indices of the last pass directly)
-static int vx_sort(const char *W, long long n, long long cells, const VxWorkspace &w, int *last_idx,
-                   const unsigned **keys, const int **idx, hipStream_t s) {
+int vx_sort(const char *W, long long n, long long cells, const VxWorkspace &w, int *last_idx,
+            const unsigned **keys, const int **idx, hipStream_t s) {
   const int passes = vx_passes(cells);
   unsigned *const kbuf[2] = {w.ka, w.kb};
   int *const ibuf[2] = {w.ia, w.ib};

@@ -781,6 +781,111 @@ class HipKernels:
                 coors_map, reduce_count, order, voxel_start, num_voxels, int(reduce_type),
                 grad_feats)
 
+    # ---- sparse 3-D convolution (include/nesie_ops.h, "mmdet3d/ops/spconv")
+    @staticmethod
+    def _triples(*triples):
+        out = []
+        for t in triples:
+            t = [int(v) for v in t]
+            assert len(t) == 3, 'three spatial dimensions only'
+            out.append((ctypes.c_int * 3)(*t))
+        return out
+
+    @staticmethod
+    def spconv_out_shape(spatial_shape, ksize, stride, padding, subm, batch_size):
+        """-> ((Do, Ho, Wo), output cells) of a sparse conv; raises on a geometry the kernels
+        refuse, a grid of 2^31 cells or more among them (nesie_spconv_out_shape)."""
+        sh, ks, st, pd = HipKernels._triples(spatial_shape, ksize, stride, padding)
+        out, cells = (ctypes.c_int * 3)(), ctypes.c_longlong()
+        _lib.call("nesie_spconv_out_shape", ctypes.addressof(sh), ctypes.addressof(ks),
+                  ctypes.addressof(st), ctypes.addressof(pd), int(bool(subm)), int(batch_size),
+                  ctypes.addressof(out), ctypes.addressof(cells))
+        return tuple(out), cells.value
+
+    @staticmethod
+    def spconv_rules_workspace_bytes(n, kvol, subm):
+        """Scratch bytes of ``spconv_out_sites``; raises on sizes the sort refuses."""
+        out = ctypes.c_longlong()
+        _lib.call("nesie_spconv_rules_workspace_bytes", n, int(kvol), int(bool(subm)),
+                  ctypes.addressof(out))
+        return out.value
+
+    def spconv_out_sites(self, indices, batch_size, spatial_shape, ksize, stride, padding, subm,
+                         sorted_keys, sorted_rows, nbr_t, out_indices, counts, workspace=None):
+        """Phase 1 of the rulebook: indices (N,4) i32 -> sorted_keys (N), sorted_rows (N),
+        nbr_t (N,K) written in full, out_indices (cap,4) rows below M (None for a submanifold conv)
+        and counts (2) = {M, offending rows} on the device (nesie_spconv_out_sites)."""
+        _check(indices, sorted_keys, sorted_rows, nbr_t, counts)
+        _i32(indices, sorted_keys, sorted_rows, nbr_t, counts)
+        n = int(indices.shape[0])
+        sh, ks, st, pd = self._triples(spatial_shape, ksize, stride, padding)
+        kvol = ks[0] * ks[1] * ks[2]
+        assert tuple(indices.shape) == (n, 4) and tuple(nbr_t.shape) == (n, kvol)
+        assert sorted_keys.numel() == n and sorted_rows.numel() == n and counts.numel() == 2
+        if out_indices is not None:
+            _check(out_indices); _i32(out_indices)
+            _, cells = self.spconv_out_shape(spatial_shape, ksize, stride, padding, subm, batch_size)
+            assert out_indices.dim() == 2 and out_indices.shape[1] == 4
+            assert out_indices.shape[0] >= min(n * kvol, cells)
+        else:
+            assert subm, 'a regular conv writes out_indices'
+        need = self.spconv_rules_workspace_bytes(n, kvol, subm)
+        workspace = self._voxel_workspace(workspace, need, indices.device)
+        _launch("nesie_spconv_out_sites", indices, n, indices, int(batch_size),
+                ctypes.addressof(sh), ctypes.addressof(ks), ctypes.addressof(st),
+                ctypes.addressof(pd), int(bool(subm)), sorted_keys, sorted_rows, nbr_t, out_indices,
+                counts, workspace)
+
+    def spconv_gather_table(self, out_indices, sorted_keys, sorted_rows, batch_size, spatial_shape,
+                            ksize, stride, padding, subm, nbr, pair_num):
+        """Phase 2 of the rulebook: out_indices (M,4) -> nbr (M,K) written in full and pair_num (K)
+        (nesie_spconv_gather_table)."""
+        _check(out_indices, sorted_keys, sorted_rows, nbr, pair_num)
+        _i32(out_indices, sorted_keys, sorted_rows, nbr, pair_num)
+        m, n = int(out_indices.shape[0]), int(sorted_keys.numel())
+        sh, ks, st, pd = self._triples(spatial_shape, ksize, stride, padding)
+        kvol = ks[0] * ks[1] * ks[2]
+        assert tuple(out_indices.shape) == (m, 4) and tuple(nbr.shape) == (m, kvol)
+        assert sorted_rows.numel() == n and pair_num.numel() == kvol
+        _launch("nesie_spconv_gather_table", out_indices, m, out_indices, n, sorted_keys,
+                sorted_rows, int(batch_size), ctypes.addressof(sh), ctypes.addressof(ks),
+                ctypes.addressof(st), ctypes.addressof(pd), int(bool(subm)), nbr, pair_num)
+
+    def spconv_gather_gemm(self, src, weight, table, dst, weight_transposed=False):
+        """dst[r] = sum_k src[table[r, k]] . W[k] (nesie_spconv_gather_gemm): src (S, c_src),
+        table (R, K) i32 with entries in -1 .. S - 1, dst (R, c_dst) written in full; weight
+        (..., c_src, c_dst) with K leading elements, or (..., c_dst, c_src) read transposed."""
+        _check(src, weight, table, dst); _f32(src, weight, dst); _i32(table)
+        rows, kvol = (int(s) for s in table.shape)
+        c_src, c_dst = int(src.shape[1]), int(dst.shape[1])
+        assert src.dim() == 2 and tuple(dst.shape) == (rows, c_dst)
+        tail = (c_dst, c_src) if weight_transposed else (c_src, c_dst)
+        assert tuple(weight.shape[-2:]) == tail and weight.numel() == kvol * c_src * c_dst
+        _launch("nesie_spconv_gather_gemm", dst, rows, int(src.shape[0]), kvol, c_src, c_dst, src,
+                weight, bool(weight_transposed), table, dst)
+
+    @staticmethod
+    def spconv_wgrad_workspace_bytes(rows, kvol, c_in, c_out):
+        out = ctypes.c_longlong()
+        _lib.call("nesie_spconv_wgrad_workspace_bytes", rows, int(kvol), int(c_in), int(c_out),
+                  ctypes.addressof(out))
+        return out.value
+
+    def spconv_wgrad(self, src, dout, table, dw, workspace=None):
+        """dw[k] = sum_r src[table[r, k]]^T . dout[r] (nesie_spconv_wgrad): src (S, c_in),
+        dout (R, c_out), table (R, K) i32, dw (..., c_in, c_out) with K leading elements, written
+        in full in a fixed order."""
+        _check(src, dout, table, dw); _f32(src, dout, dw); _i32(table)
+        rows, kvol = (int(s) for s in table.shape)
+        c_in, c_out = int(src.shape[1]), int(dout.shape[1])
+        assert src.dim() == 2 and tuple(dout.shape) == (rows, c_out)
+        assert tuple(dw.shape[-2:]) == (c_in, c_out) and dw.numel() == kvol * c_in * c_out
+        assert rows > 0 and src.shape[0] > 0, 'an empty product is zeros: the caller writes them'
+        need = self.spconv_wgrad_workspace_bytes(rows, kvol, c_in, c_out)
+        workspace = self._voxel_workspace(workspace, need, src.device)
+        _launch("nesie_spconv_wgrad", dw, rows, int(src.shape[0]), kvol, c_in, c_out, src, dout,
+                table, dw, workspace)
+
     def vote_targets(self, points, gt_boxes, gt_count):
         """points (B,N,C>=3), depth-frame gt_boxes (B,T,7), gt_count (B) int64 -> vote targets
         (B,N,9) and masks (B,N) int64 of get_targets_single, one launch."""

@@ -1,6 +1,6 @@
 """Host-side mirror of ``mmdet3d.ops`` for the VoteNet/Nesie hot path
 (reference mmdet3d/ops/__init__.py:5-41).  Hot-path names are real; the rest of
-the reference's ``__all__`` (spconv / paconv ...) resolves to stubs that
+the reference's ``__all__`` (paconv, SparseBottleneck ...) resolves to stubs that
 raise on use, so ``from mmdet3d.ops import X``
 style code keeps importing ("import-time requirement").
 """
@@ -19,6 +19,7 @@ from .iou3d import batched_nms_bev, boxes_iou_bev, boxes_overlap_bev, nms_gpu, n
 from .roiaware_pool3d import (RoIAwarePool3d, points_in_boxes_batch, points_in_boxes_count,
                               points_in_boxes_cpu, points_in_boxes_gpu)
 from .rotated_iou import cal_giou_3d, cal_iou_3d, sort_v
+from .sparse_block import SparseBasicBlock, make_sparse_convmodule
 from .voxel import DynamicScatter, Voxelization, dynamic_scatter, voxelization
 
 _HOT = [
@@ -31,12 +32,13 @@ _HOT = [
     'AxisAlignedBboxOverlaps3D', 'axis_aligned_bbox_overlaps_3d',
     'RoIAwarePool3d', 'points_in_boxes_gpu', 'points_in_boxes_cpu',
     'Voxelization', 'voxelization', 'dynamic_scatter', 'DynamicScatter',
+    'SparseBasicBlock', 'make_sparse_convmodule',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
     'get_compiling_cuda_version', 'NaiveSyncBatchNorm1d', 'NaiveSyncBatchNorm2d',
-    'batched_nms', 'sigmoid_focal_loss', 'SigmoidFocalLoss', 'SparseBasicBlock',
-    'SparseBottleneck', 'make_sparse_convmodule', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
+    'batched_nms', 'sigmoid_focal_loss', 'SigmoidFocalLoss',
+    'SparseBottleneck', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
     'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule', 'PAConvCUDASAModuleMSG',
 ]
 __all__ = _HOT + _OUT_OF_SCOPE
