@@ -1085,6 +1085,50 @@ int nesie_spconv_wgrad(long long rows, long long src_rows, int kvol, int c_in, i
                        const float *src, const float *dout, const int *table, float *dw,
                        void *workspace, void *stream);
 
+/* mmdet3d/ops/paconv/src/assign_score_withk_cuda.cu:38-141  assign_score_withk forward / backward
+ * (PAConv's aggregation of a position-adaptive weight bank over a neighbourhood).
+ * Sizes: b, n0 source points, n1 centres, k neighbours, m bank kernels, o output channels.
+ *   points[B,N0,M,O]  centers[B,N0,M,O]  scores[B,N1,K,M]  knn_idx[B,N1,K] (int64, as the reference)
+ * With kn = knn_idx[b,n,k] and cn = knn_idx[b,n,0], the pair (n,k) is VALID iff 0 <= kn < N0.
+ * forward:  output[b,o,n,k] = sum_m scores[b,n,k,m] * (points[b,kn,m,o] - centers[b,cn,m,o]) for a
+ *   valid pair, exactly 0.0f for an invalid one; layout (B,O,N1,K); per element one chain
+ *   acc = fma(score, point - centre, acc) with m ascending; WRITTEN in full.
+ * backward (any of the three gradient pointers may be NULL = not wanted):
+ *   grad_scores[b,n,k,m]  = sum_o (points[b,kn,m,o] - centers[b,cn,m,o]) * grad_out[b,o,n,k], one
+ *     fma chain with o ascending; exactly 0 for an invalid pair;
+ *   grad_points[b,j,m,o]  = sum over the valid (n,k) with kn == j of scores[b,n,k,m] *
+ *     grad_out[b,o,n,k], one fma chain in ascending n*K + k;
+ *   grad_centers[b,j,m,o] = - (sum over the n with cn == j, over their valid k, of the same
+ *     product), one fma chain in ascending n*K + k, negated at the end;
+ *   all three WRITTEN in full: a point that nobody references gets zeros.
+ * The reference's `aggregate` argument does not reach its kernels and has no counterpart here.
+ * Departures from the reference:
+ *   - it asserts cn < N0 and otherwise reads out of bounds; here the centre term of an out-of-range
+ *     cn is dropped (a zero row) in forward and backward (k = 0 then has kn = cn invalid and is zero
+ *     anyway);
+ *   - it adds points * score - centers * score per m; here the difference is taken first;
+ *   - its output and gradients are atomicAdd sums in arrival order; here the order of every sum is
+ *     fixed, two runs give the same bits, there is no atomic variant and NESIE_DETERMINISTIC=0
+ *     changes nothing.
+ * The scatter goes through nesie_inverted_index over N0 + 1 sources (invalid entries sit in the
+ * sentinel bucket N0, which is skipped).  Scratch comes from the caller (16-byte aligned, at least
+ * nesie_assign_score_withk_backward_workspace_bytes); nothing allocates or synchronises, so both
+ * calls capture into a graph.
+ * A negative size or k, m or o <= 0 is NESIE_ERR_INVALID_ARG; an element count of any tensor at or
+ * above 2^31 is NESIE_ERR_UNSUPPORTED (workspace_bytes then answers 0); both before any launch.
+ * b, n1 or n0 == 0 succeeds without a launch. */
+int nesie_assign_score_withk_forward(int b, int n0, int n1, int k, int m, int o,
+                                     const float *points, const float *centers,
+                                     const float *scores, const long long *knn_idx, float *output,
+                                     void *stream);
+size_t nesie_assign_score_withk_backward_workspace_bytes(int b, int n0, int n1, int k, int m, int o);
+int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, int m, int o,
+                                      const float *grad_out, const float *points,
+                                      const float *centers, const float *scores,
+                                      const long long *knn_idx, float *grad_points,
+                                      float *grad_centers, float *grad_scores, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

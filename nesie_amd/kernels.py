@@ -1731,6 +1731,39 @@ class HipKernels:
         _launch("nesie_bn_relu_backward", x, b, c, p, dy, x, y, gamma, beta, save_mean, save_invstd,
                 fwd_coef, bool(relu), dx, dgamma, dbeta, row_bias, group, d_row_bias, ws, need)
 
+    def assign_score_withk_forward(self, b, n0, n1, m, k, o, points, centers, scores, knn_idx,
+                                   output):
+        """output (B, O, N1, K) <- sum_m scores * (points[knn_idx] - centers[knn_idx[..., 0]]),
+        WRITTEN in full (nesie_assign_score_withk_forward; the size order is the reference
+        wrapper's B, N0, N1, M, K, O)."""
+        _check(points, centers, scores, knn_idx, output); _f32(points, centers, scores, output)
+        if knn_idx.dtype != torch.int64:
+            raise TypeError(f"expected int64, got {knn_idx.dtype}")
+        assert points.numel() == b * n0 * m * o and centers.numel() == b * n0 * m * o
+        assert scores.numel() == b * n1 * k * m and knn_idx.numel() == b * n1 * k
+        assert output.numel() == b * o * n1 * k
+        _launch("nesie_assign_score_withk_forward", output, b, n0, n1, k, m, o, points, centers,
+                scores, knn_idx, output)
+
+    def assign_score_withk_backward(self, b, n0, n1, m, k, o, grad_out, points, centers, scores,
+                                    knn_idx, grad_points, grad_centers, grad_scores):
+        """grad_points / grad_centers (B, N0, M, O) and grad_scores (B, N1, K, M), each WRITTEN in
+        full in a fixed order, or None = skipped (nesie_assign_score_withk_backward)."""
+        _check(grad_out, points, centers, scores, knn_idx); _f32(grad_out, points, centers, scores)
+        if knn_idx.dtype != torch.int64:
+            raise TypeError(f"expected int64, got {knn_idx.dtype}")
+        assert points.numel() == b * n0 * m * o and centers.numel() == b * n0 * m * o
+        assert scores.numel() == b * n1 * k * m and knn_idx.numel() == b * n1 * k
+        assert grad_out.numel() == b * o * n1 * k
+        for g, like in ((grad_points, points), (grad_centers, centers), (grad_scores, scores)):
+            if g is not None:
+                _check(g); _f32(g)
+                assert g.numel() == like.numel()
+        need = _lib.load().nesie_assign_score_withk_backward_workspace_bytes(b, n0, n1, k, m, o)
+        ws = _workspace(need, grad_out.device)
+        _launch("nesie_assign_score_withk_backward", grad_out, b, n0, n1, k, m, o, grad_out, points,
+                centers, scores, knn_idx, grad_points, grad_centers, grad_scores, ws, need)
+
 
 def _row_bias_group(x, row_bias):
     if row_bias is None:

@@ -1,8 +1,17 @@
 """Host-side mirror of ``mmdet3d.ops`` for the VoteNet/Nesie hot path
 (reference mmdet3d/ops/__init__.py:5-41).  Hot-path names are real; the rest of
-the reference's ``__all__`` (paconv, SparseBottleneck ...) resolves to stubs that
+the reference's ``__all__`` (RoIAlign, SparseBottleneck ...) resolves to stubs that
 raise on use, so ``from mmdet3d.ops import X``
 style code keeps importing ("import-time requirement").
+
+PAConv is real, with one wrinkle in its spelling.  The top-level names ``assign_score_withk``,
+``PAConv`` and ``SparseBottleneck`` were published as raising stubs and the suite pins them as
+such, so they stay in ``_OUT_OF_SCOPE`` and keep raising ``NotImplementedError`` (the message
+points here); the real ``assign_score_withk``, ``PAConv`` and ``PAConvCUDA`` live in the
+subpackage ``nesie_amd.mmdet3d_ops.paconv``, which mirrors ``mmdet3d.ops.paconv``:
+``from nesie_amd.mmdet3d_ops.paconv import PAConv, assign_score_withk``.  ``PAConvCUDA`` and the
+four set-abstraction modules ``PAConv{,CUDA}SAModule{,MSG}`` were pinned by nothing and are real
+at the top level (``_HOT``); ``build_sa_module`` builds them.
 """
 from .axis_aligned_iou import AxisAlignedBboxOverlaps3D, axis_aligned_bbox_overlaps_3d
 from .ball_query import ball_query
@@ -21,6 +30,9 @@ from .roiaware_pool3d import (RoIAwarePool3d, points_in_boxes_batch, points_in_b
 from .rotated_iou import cal_giou_3d, cal_iou_3d, sort_v
 from .sparse_block import SparseBasicBlock, make_sparse_convmodule
 from .voxel import DynamicScatter, Voxelization, dynamic_scatter, voxelization
+from .paconv import PAConvCUDA
+from .paconv_sa_module import (PAConvCUDASAModule, PAConvCUDASAModuleMSG, PAConvSAModule,
+                               PAConvSAModuleMSG)
 
 _HOT = [
     'ball_query', 'furthest_point_sample', 'furthest_point_sample_with_dist',
@@ -33,20 +45,26 @@ _HOT = [
     'RoIAwarePool3d', 'points_in_boxes_gpu', 'points_in_boxes_cpu',
     'Voxelization', 'voxelization', 'dynamic_scatter', 'DynamicScatter',
     'SparseBasicBlock', 'make_sparse_convmodule',
+    'PAConvCUDA', 'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule',
+    'PAConvCUDASAModuleMSG',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
     'get_compiling_cuda_version', 'NaiveSyncBatchNorm1d', 'NaiveSyncBatchNorm2d',
     'batched_nms', 'sigmoid_focal_loss', 'SigmoidFocalLoss',
-    'SparseBottleneck', 'assign_score_withk', 'PAConv', 'PAConvCUDA',
-    'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule', 'PAConvCUDASAModuleMSG',
+    'SparseBottleneck', 'assign_score_withk', 'PAConv',
 ]
+_IN_SUBPACKAGE = {'assign_score_withk': 'paconv', 'PAConv': 'paconv'}
 __all__ = _HOT + _OUT_OF_SCOPE
 
 
 def __getattr__(name):
     if name in _OUT_OF_SCOPE:
         def _stub(*args, **kwargs):
+            if name in _IN_SUBPACKAGE:
+                raise NotImplementedError(
+                    f'the top-level name mmdet3d.ops.{name} stays a stub; import the real one '
+                    f'from nesie_amd.mmdet3d_ops.{_IN_SUBPACKAGE[name]}')
             raise NotImplementedError(
                 f'mmdet3d.ops.{name} is outside the VoteNet/Nesie hot path this build '
                 'covers (SURVEY.md section 2a/2b)')
