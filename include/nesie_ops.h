@@ -1129,6 +1129,54 @@ int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, int m, int o
                                       float *grad_centers, float *grad_scores, void *workspace,
                                       size_t workspace_bytes, void *stream);
 
+/* Sigmoid focal loss (mmcv ops sigmoid_focal_loss; mmdet FocalLoss builds on it).  The mmcv source is
+ * not in the reference tree: the formulas below are the specification.
+ *   x[N,C] logits, target[N] int64 labels.  Element (n, c) is POSITIVE iff target[n] == c; a label
+ *   outside [0, C) (mmdet's background label C, -1, anything) makes the whole row negative and is
+ *   never used as an index.  With z = x, a = alpha for a positive element and z = -x,
+ *   a = 1 - alpha for a negative one, and softplus(v) = max(v, 0) + log1p(exp(-|v|)):
+ *     term      = a * exp(-gamma * softplus(z)) * softplus(-z)        (= -a (1 - p_t)^gamma log p_t)
+ *     d term/dz = -a * exp(-gamma * softplus(z)) * (gamma * sigmoid(z) * softplus(-z) + sigmoid(-z))
+ *   and d term/dx carries the sign of dz/dx.  Nothing is subtracted or clamped, so every finite
+ *   logit gives a finite term and gradient for every gamma >= 0 (gamma = 0: alpha-weighted BCE).
+ * Weights: class_weight (C,) or NULL scales row n by class_weight[target[n]], by 1.0 for a label
+ *   outside [0, C) (mmcv reads out of bounds there); sample_weight is NULL (sample_weight_mode 0),
+ *   (N,) per row (mode 1) or (N, C) per element (mode 2).
+ * Departure in value from mmcv: it clamps log() at FLT_MIN, so its loss stops growing at
+ *   |x| ~ 87.3 and its gradient drops to 0 beyond; here the loss keeps growing linearly in -z and
+ *   d term/dz keeps its limit -a, for every gamma.
+ *   forward      loss[N,C] = term * weights * scale, every element written.
+ *   forward_sum  out[0] = (sum of term * weights over all N * C elements) * scale * (*scale_dev),
+ *                scale_dev a one-element device tensor or NULL (= 1); the (N, C) loss is never
+ *                stored.  The sum runs in a fixed order that depends on N * C only (chunks of 4096
+ *                elements, a fixed tree inside a chunk, then the chunks' partials in a fixed order):
+ *                no atomics, the same bits whatever the CU budget or the stream.  workspace: at
+ *                least nesie_sigmoid_focal_loss_workspace_bytes(n, c) bytes, 4-byte aligned; may be
+ *                NULL when that is 0 (a single chunk: one launch instead of two).
+ *   backward     grad_x[N,C] = d term/dx * weights * upstream, every element written in one launch;
+ *                upstream = grad_out[n,c] * scale * (*scale_dev) with grad_out (N, C), or
+ *                (*grad_scalar) * scale * (*scale_dev) with a one-element device tensor: exactly one
+ *                of grad_out / grad_scalar is non-NULL, both are read on the device.
+ * Nothing allocates or synchronises: all three capture into a graph.  n == 0 or c == 0 succeeds
+ * without a launch and touches nothing.  A negative size, gamma < 0 or NaN, a mode outside 0..2 or
+ * one that disagrees with sample_weight, or a null x / target / output of a non-empty problem is
+ * NESIE_ERR_INVALID_ARG; n * c >= 2^31 is NESIE_ERR_UNSUPPORTED (workspace_bytes then answers 0). */
+int nesie_sigmoid_focal_loss_forward(int n, int c, const float *x, const long long *target,
+                                     const float *class_weight, const float *sample_weight,
+                                     int sample_weight_mode, float gamma, float alpha, float scale,
+                                     float *loss, void *stream);
+size_t nesie_sigmoid_focal_loss_workspace_bytes(int n, int c);
+int nesie_sigmoid_focal_loss_forward_sum(int n, int c, const float *x, const long long *target,
+                                         const float *class_weight, const float *sample_weight,
+                                         int sample_weight_mode, float gamma, float alpha,
+                                         float scale, const float *scale_dev, float *out,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+int nesie_sigmoid_focal_loss_backward(int n, int c, const float *x, const long long *target,
+                                      const float *class_weight, const float *sample_weight,
+                                      int sample_weight_mode, float gamma, float alpha,
+                                      const float *grad_out, const float *grad_scalar, float scale,
+                                      const float *scale_dev, float *grad_x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

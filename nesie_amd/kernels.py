@@ -1764,6 +1764,69 @@ class HipKernels:
         _launch("nesie_assign_score_withk_backward", grad_out, b, n0, n1, k, m, o, grad_out, points,
                 centers, scores, knn_idx, grad_points, grad_centers, grad_scores, ws, need)
 
+    @staticmethod
+    def _focal_operands(input, target, weight, sample_weight):
+        """Checks of the operands the three focal-loss entries share -> (n, c, sample-weight mode:
+        0 none, 1 one weight per row (N,), 2 one per element (N, C) or any shape of N * C)."""
+        _check(input, target); _f32(input)
+        if target.dtype != torch.int64:
+            raise TypeError(f"expected int64, got {target.dtype}")
+        assert input.dim() == 2 and target.numel() == input.shape[0]
+        n, c = input.shape
+        if weight is not None:
+            _check(weight); _f32(weight)
+            assert weight.numel() == c
+        mode = 0
+        if sample_weight is not None:
+            _check(sample_weight); _f32(sample_weight)
+            assert sample_weight.numel() in (n, n * c)
+            mode = 1 if sample_weight.numel() == n else 2
+        return n, c, mode
+
+    def sigmoid_focal_loss_forward(self, input, target, weight, output, gamma, alpha,
+                                   sample_weight=None, scale=1.0):
+        """output (N, C) <- focal term * weight[target] * sample_weight * scale, WRITTEN in full
+        (nesie_sigmoid_focal_loss_forward; the leading six arguments are mmcv's)."""
+        n, c, mode = self._focal_operands(input, target, weight, sample_weight)
+        _check(output); _f32(output)
+        assert output.numel() == n * c
+        _launch("nesie_sigmoid_focal_loss_forward", input, n, c, input, target, weight,
+                sample_weight, mode, float(gamma), float(alpha), float(scale), output)
+
+    def sigmoid_focal_loss_forward_sum(self, input, target, weight, output, gamma, alpha,
+                                       sample_weight=None, scale=1.0, scale_dev=None):
+        """output (one element) <- sum of the weighted focal terms * scale * scale_dev[0], in a
+        fixed order; the (N, C) loss is never stored (nesie_sigmoid_focal_loss_forward_sum)."""
+        n, c, mode = self._focal_operands(input, target, weight, sample_weight)
+        _check(output); _f32(output)
+        assert output.numel() == 1
+        if scale_dev is not None:
+            _check(scale_dev); _f32(scale_dev)
+            assert scale_dev.numel() == 1
+        need = _lib.load().nesie_sigmoid_focal_loss_workspace_bytes(n, c)
+        ws = _workspace(need, input.device) if need else None    # a single chunk needs no scratch
+        _launch("nesie_sigmoid_focal_loss_forward_sum", input, n, c, input, target, weight,
+                sample_weight, mode, float(gamma), float(alpha), float(scale), scale_dev, output,
+                ws, need)
+
+    def sigmoid_focal_loss_backward(self, input, target, weight, grad_input, gamma, alpha,
+                                    sample_weight=None, grad_output=None, grad_scalar=None,
+                                    scale=1.0, scale_dev=None):
+        """grad_input (N, C) <- d term/d input * weights * upstream, WRITTEN in full in one launch;
+        upstream is grad_output (N, C) or the one-element grad_scalar, read on the device, times
+        scale * scale_dev[0] (nesie_sigmoid_focal_loss_backward)."""
+        n, c, mode = self._focal_operands(input, target, weight, sample_weight)
+        _check(grad_input); _f32(grad_input)
+        assert grad_input.numel() == n * c
+        assert (grad_output is None) != (grad_scalar is None)
+        for t, count in ((grad_output, n * c), (grad_scalar, 1), (scale_dev, 1)):
+            if t is not None:
+                _check(t); _f32(t)
+                assert t.numel() == count
+        _launch("nesie_sigmoid_focal_loss_backward", input, n, c, input, target, weight,
+                sample_weight, mode, float(gamma), float(alpha), grad_output, grad_scalar,
+                float(scale), scale_dev, grad_input)
+
 
 def _row_bias_group(x, row_bias):
     if row_bias is None:

@@ -1,8 +1,10 @@
-"""Host-side mirror of ``mmdet3d.ops`` for the VoteNet/Nesie hot path
-(reference mmdet3d/ops/__init__.py:5-41).  Hot-path names are real; the rest of
-the reference's ``__all__`` (RoIAlign, SparseBottleneck ...) resolves to stubs that
-raise on use, so ``from mmdet3d.ops import X``
-style code keeps importing ("import-time requirement").
+"""Host-side mirror of ``mmdet3d.ops`` (reference mmdet3d/ops/__init__.py:1-41).  The reference's
+own operator families are real, and so is the one mmcv re-export that sits on a training path:
+``sigmoid_focal_loss`` / ``SigmoidFocalLoss`` (``focal_loss.py``, the kernel behind mmdet's
+``FocalLoss``).  The rest of the reference's ``__all__`` (the other mmcv re-exports: nms, RoIAlign,
+NaiveSyncBatchNorm ..., and SparseBottleneck) resolves to stubs that raise on use, so
+``from mmdet3d.ops import X`` style code keeps importing ("import-time
+requirement").
 
 PAConv is real, with one wrinkle in its spelling.  The top-level names ``assign_score_withk``,
 ``PAConv`` and ``SparseBottleneck`` were published as raising stubs and the suite pins them as
@@ -31,6 +33,7 @@ from .rotated_iou import cal_giou_3d, cal_iou_3d, sort_v
 from .sparse_block import SparseBasicBlock, make_sparse_convmodule
 from .voxel import DynamicScatter, Voxelization, dynamic_scatter, voxelization
 from .paconv import PAConvCUDA
+from .focal_loss import SigmoidFocalLoss, sigmoid_focal_loss
 from .paconv_sa_module import (PAConvCUDASAModule, PAConvCUDASAModuleMSG, PAConvSAModule,
                                PAConvSAModuleMSG)
 
@@ -46,12 +49,12 @@ _HOT = [
     'Voxelization', 'voxelization', 'dynamic_scatter', 'DynamicScatter',
     'SparseBasicBlock', 'make_sparse_convmodule',
     'PAConvCUDA', 'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule',
-    'PAConvCUDASAModuleMSG',
+    'PAConvCUDASAModuleMSG', 'sigmoid_focal_loss', 'SigmoidFocalLoss',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
     'get_compiling_cuda_version', 'NaiveSyncBatchNorm1d', 'NaiveSyncBatchNorm2d',
-    'batched_nms', 'sigmoid_focal_loss', 'SigmoidFocalLoss',
+    'batched_nms',
     'SparseBottleneck', 'assign_score_withk', 'PAConv',
 ]
 _IN_SUBPACKAGE = {'assign_score_withk': 'paconv', 'PAConv': 'paconv'}

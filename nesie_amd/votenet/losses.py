@@ -1,15 +1,19 @@
 """Losses of the Nesie head.
 
 Restates ``mmdet3d/models/losses/{chamfer_distance,surface_loss,side_pred_loss,
-iou3d_loss,axis_aligned_iou_loss,gfocal_loss}.py`` and the mmdet 2.19 loss plumbing they call
-(``weighted_loss`` / ``weight_reduce_loss`` / MSE / L1 / SmoothL1 / CrossEntropy;
-source not in the reference tree, semantics from SURVEY.md appendix C).
+iou3d_loss,axis_aligned_iou_loss,gfocal_loss}.py`` and the mmdet 2.19 losses and loss plumbing they
+stand beside (``weighted_loss`` / ``weight_reduce_loss`` / MSE / L1 / SmoothL1 / CrossEntropy /
+FocalLoss; source not in the reference tree, semantics from SURVEY.md appendix C).
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
+from ..kernels import backend_for, injected_backend
 from ..mmdet3d_ops.axis_aligned_iou import axis_aligned_bbox_overlaps_3d
+from ..mmdet3d_ops.focal_loss import focal_backward, focal_forward
 from ..mmdet3d_ops.rotated_iou import cal_diou_3d, cal_giou_3d, cal_iou_3d
 
 
@@ -330,7 +334,159 @@ class GeneralQualityFocalLoss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
+# ---- distribution focal loss (gfocal_loss.py:54-76, 143-197) ---------------------
+def distribution_focal_loss(pred, label, weight=None, reduction='mean', avg_factor=None):
+    """pred (N, n+1) logits over the integral set, label (N,) real distances in [0, n): the two
+    neighbouring integers' cross entropies, weighted by the distance to the other one -> weighted
+    and reduced as ``weighted_loss`` does."""
+    dis_left = label.long()
+    dis_right = dis_left + 1
+    weight_left = dis_right.float() - label
+    weight_right = label - dis_left.float()
+    loss = F.cross_entropy(pred, dis_left, reduction='none') * weight_left \
+        + F.cross_entropy(pred, dis_right, reduction='none') * weight_right
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+class GeneralDistributionFocalLoss(nn.Module):
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * distribution_focal_loss(
+            pred, target, weight, reduction=reduction, avg_factor=avg_factor)
+
+
+# ---- sigmoid focal loss (mmdet focal_loss.py; formulas of include/nesie_ops.h) ----
+class _FocalTerms(Function):
+    """Elementwise focal loss of logits against a boolean one-hot mask, in tensor ops of any dtype
+    and device.  Forward and backward are the softplus formulas written out: autograd through
+    ``max`` / ``abs`` would halve or double the slope at x == 0, and through ``exp`` it forms
+    ``inf * 0`` at |x| ~ 3e38."""
+
+    @staticmethod
+    def _parts(pred, positive, gamma, alpha):
+        z = torch.where(positive, pred, -pred)
+        a = torch.where(positive, pred.new_tensor(alpha), pred.new_tensor(1 - alpha))
+        e = torch.exp(-z.abs())
+        log1p_e = torch.log1p(e)
+        sp_pos = z.clamp(min=0) + log1p_e            # softplus(z)
+        sp_neg = (-z).clamp(min=0) + log1p_e         # softplus(-z)
+        return z, e, sp_neg, a * torch.exp(-(gamma * sp_pos))
+
+    @staticmethod
+    def forward(ctx, pred, positive, gamma, alpha):
+        ctx.save_for_backward(pred, positive)
+        ctx.gamma, ctx.alpha = gamma, alpha
+        _, _, sp_neg, w = _FocalTerms._parts(pred, positive, gamma, alpha)
+        return w * sp_neg
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        pred, positive = ctx.saved_tensors
+        z, e, sp_neg, w = _FocalTerms._parts(pred, positive, ctx.gamma, ctx.alpha)
+        r = 1 / (1 + e)
+        s_pos = torch.where(z >= 0, r, e * r)        # sigmoid(z)
+        s_neg = torch.where(z >= 0, e * r, r)        # sigmoid(-z)
+        dz = w * (ctx.gamma * s_pos * sp_neg + s_neg)
+        return grad * torch.where(positive, -dz, dz), None, None, None
+
+
+def py_sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reduction='mean',
+                          avg_factor=None):
+    """mmdet's tensor-op focal loss on the stable formulas.  pred (N, C) logits; target (N, C)
+    one-hot (bool or any number type, positive where non-zero); weight (N,), (N, C) or of N * C
+    elements."""
+    loss = _FocalTerms.apply(pred, target != 0, float(gamma), float(alpha))
+    if weight is not None:
+        if weight.shape != loss.shape:
+            if weight.size(0) == loss.size(0):
+                # one weight per sample: broadcast over the classes
+                weight = weight.view(-1, 1)
+            else:
+                assert weight.numel() == loss.numel()
+                weight = weight.view(loss.size(0), -1)
+        assert weight.dim() == loss.dim()
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+class FocalLoss(nn.Module):
+    """mmdet's ``FocalLoss`` for integer labels: pred (N, C), target (N,) with any value outside
+    [0, C) as background.  float32 tensors served by the HIP back end go through
+    ``csrc/focal_loss.hip`` (reduced forward fused, backward one launch, ``'none'`` with the weight
+    applied in the launch); every other dtype and device, an empty input and a weight that requires a
+    gradient take ``py_sigmoid_focal_loss``."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid focal loss supported now.'
+        self.use_sigmoid = use_sigmoid
+        self.gamma = gamma
+        self.alpha = alpha
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    @staticmethod
+    def _native(pred):
+        if pred.dtype != torch.float32 or not (pred.is_cuda or injected_backend() is not None):
+            return False
+        return getattr(backend_for(pred), 'name', '') == 'hip'
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        # the kernels differentiate the logits only: a weight or avg_factor that wants a gradient
+        # goes through autograd
+        wants_grad = any(torch.is_tensor(v) and v.requires_grad for v in (weight, avg_factor))
+        if pred.numel() == 0 or wants_grad or not self._native(pred):
+            num_classes = pred.size(1)
+            onehot = target.view(-1, 1) == torch.arange(num_classes, device=pred.device)
+            return self.loss_weight * py_sigmoid_focal_loss(
+                pred, onehot, weight, self.gamma, self.alpha, reduction, avg_factor)
+        if avg_factor is not None and reduction == 'sum':
+            raise ValueError('avg_factor can not be used with reduction="sum"')
+        n, c = pred.shape
+        if weight is not None:
+            assert weight.size(0) == n or weight.numel() == n * c
+            weight = weight.to(torch.float32).contiguous()
+        scale, scale_dev = float(self.loss_weight), None
+        if reduction == 'mean':
+            if avg_factor is None:
+                scale /= n * c
+            elif torch.is_tensor(avg_factor):
+                # the kernels multiply by the device scalar: one small launch for its reciprocal
+                scale_dev = avg_factor.to(pred.device, torch.float32).reshape(1).reciprocal()
+            else:
+                scale /= avg_factor
+        return _FocalLossFn.apply(pred, target, weight, float(self.gamma), float(self.alpha),
+                                  reduction != 'none', scale, scale_dev)
+
+
+class _FocalLossFn(Function):
+    @staticmethod
+    def forward(ctx, pred, target, sample_weight, gamma, alpha, reduce, scale, scale_dev):
+        pred, target = pred.contiguous(), target.long().contiguous()
+        ctx.save_for_backward(pred, target, sample_weight, scale_dev)
+        ctx.args = (gamma, alpha, reduce, scale)
+        return focal_forward(pred, target, None, sample_weight, gamma, alpha, reduce, scale,
+                             scale_dev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        pred, target, sample_weight, scale_dev = ctx.saved_tensors
+        gamma, alpha, reduce, scale = ctx.args
+        return (focal_backward(grad, pred, target, None, sample_weight, gamma, alpha, reduce,
+                               scale, scale_dev),) + (None,) * 7
+
+
 _LOSSES = dict(ChamferDistance=ChamferDistance, CrossEntropyLoss=CrossEntropyLoss,
+               FocalLoss=FocalLoss, GeneralDistributionFocalLoss=GeneralDistributionFocalLoss,
                IoU3DLoss=IoU3DLoss, GIoU3DLoss=GIoU3DLoss, DIoU3DLoss=DIoU3DLoss,
                AxisAlignedIoULoss=AxisAlignedIoULoss,
                GeneralQualityFocalLoss=GeneralQualityFocalLoss,

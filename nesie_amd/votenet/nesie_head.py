@@ -24,10 +24,20 @@ from .bbox_module import ReliableConvBboxHead
 from .boxes import DepthInstance3DBoxes, depth_to_lidar_boxes, depth_to_lidar_points
 from . import head_loss
 from ..mmdet3d_ops.axis_aligned_iou import axis_aligned_bbox_overlaps_3d
-from .losses import build_loss, centre_size_to_corners
+from .losses import FocalLoss, build_loss, centre_size_to_corners
 from ..streams import fork_join
 from .side_pooling import SidePooling
 from .vote_module import VoteModule
+
+
+def class_term(loss, scores, targets, weight):
+    """One classification term of the head: scores (B, K, C) logits, targets and weight (B, K).
+    A ``FocalLoss`` takes rows, (B*K, C) against (B*K,); every other loss gets the (B, C, K)
+    layout it always got."""
+    if isinstance(loss, FocalLoss):
+        return loss(scores.reshape(-1, scores.shape[-1]), targets.reshape(-1),
+                    weight=weight.reshape(-1))
+    return loss(scores.transpose(2, 1), targets, weight=weight)
 
 
 class Integral(nn.Module):
@@ -408,11 +418,10 @@ class NesieHead(nn.Module):
             vote_loss = self.vote_module.get_loss(
                 bbox_preds['seed_points'], bbox_preds['vote_points'], bbox_preds['seed_indices'],
                 vote_target_masks, vote_targets)
-            objectness_loss = self.objectness_loss(
-                bbox_preds['obj_scores'].transpose(2, 1), objectness_targets,
-                weight=objectness_weights)
-            semantic_loss = self.semantic_loss(
-                bbox_preds['sem_scores'].transpose(2, 1), mask_targets, weight=box_loss_weights)
+            objectness_loss = class_term(self.objectness_loss, bbox_preds['obj_scores'],
+                                         objectness_targets, objectness_weights)
+            semantic_loss = class_term(self.semantic_loss, bbox_preds['sem_scores'],
+                                       mask_targets, box_loss_weights)
             return vote_loss, objectness_loss, semantic_loss
 
         def branch_surface():
@@ -542,8 +551,8 @@ class NesieHead(nn.Module):
         s2t, t2s = self.center_loss(bbox_preds['bbox_preds'][..., :3], center_targets,
                                     src_weight=box_loss_weights, dst_weight=valid_gt_weights)
         unsup_center_loss = s2t + t2s
-        unsup_semantic_loss = self.semantic_loss(
-            bbox_preds['sem_scores'].transpose(2, 1), mask_targets, weight=box_loss_weights)
+        unsup_semantic_loss = class_term(self.semantic_loss, bbox_preds['sem_scores'],
+                                         mask_targets, box_loss_weights)
 
         iou_weight = (box_loss_weights * pseudo_quality_mean).reshape(-1)
         unsup_iou_loss = self.iou_loss(bbox_preds['bbox_preds'].reshape(-1, 7),

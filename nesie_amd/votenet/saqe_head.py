@@ -22,7 +22,7 @@ from torch.nn import functional as F
 from ..mmdet3d_ops.rotated_iou import cal_iou_3d
 from .bbox_module import ReliableConvBboxHead
 from .losses import Bbox2Surface, build_loss
-from .nesie_head import Integral, NesieHead
+from .nesie_head import Integral, NesieHead, class_term
 from .quality_estimation import QualityEstimation
 
 
@@ -106,12 +106,9 @@ class SAQEHead(NesieHead):
 
     # ---- shared pieces of the three losses -----------------------------------------------
     def _objectness(self, bbox_preds, objectness_targets, objectness_weights):
-        l1 = self.objectness_loss(bbox_preds['obj_scores'].transpose(2, 1), objectness_targets,
-                                  weight=objectness_weights)
-        l2 = self.objectness_loss(bbox_preds['R_obj_scores'].transpose(2, 1), objectness_targets,
-                                  weight=objectness_weights)
-        l3 = self.objectness_loss(bbox_preds['R_obj_scores_jitter'].transpose(2, 1),
-                                  objectness_targets, weight=objectness_weights)
+        l1, l2, l3 = (class_term(self.objectness_loss, bbox_preds[k], objectness_targets,
+                                 objectness_weights)
+                      for k in ('obj_scores', 'R_obj_scores', 'R_obj_scores_jitter'))
         return l1 + (l2 + l3) * 0.5
 
     def _angle_terms(self, bbox_preds, bbox_targets_cat, w):
@@ -161,8 +158,8 @@ class SAQEHead(NesieHead):
         s2t, t2s = self.center_loss(bbox_preds['bbox_preds'][..., :3], center_targets,
                                     src_weight=box_loss_weights, dst_weight=valid_gt_weights)
         out['center_loss'] = s2t + t2s
-        out['semantic_loss'] = self.semantic_loss(bbox_preds['sem_scores'].transpose(2, 1),
-                                                  mask_targets, weight=box_loss_weights)
+        out['semantic_loss'] = class_term(self.semantic_loss, bbox_preds['sem_scores'],
+                                          mask_targets, box_loss_weights)
         surface_weight = box_loss_weights.reshape(-1).unsqueeze(-1).repeat(1, 6)
         probs = bbox_preds['bbox_probs'].permute(0, 3, 1, 2).reshape(-1, 6, self.reg_max + 1)
         surface = self.surface_loss(
