@@ -255,8 +255,7 @@ extern "C" int nesie_aa_iou3d_matrix_backward(int b, int m, int n, const float *
   if (grad1) {
     hipLaunchKernelGGL(aa_matrix_backward_rows_kernel, dim3((unsigned)row_groups),
                        dim3(64 * BR_WAVES), 0, (hipStream_t)stream, A, grad_out, grad1);
-    const int st = check_launch(W);
-    if (st != NESIE_OK) return st;
+    NESIE_LAUNCHED(W);
   }
   if (grad2) {
     hipLaunchKernelGGL(aa_matrix_backward_cols_kernel, dim3((unsigned)col_groups),

@@ -5,12 +5,13 @@
 //   blend_any_rows_kernel    dy (B, segs, c, per_seg) -> dZ^T (B, segs, per_seg, c) query-major rows
 //                            through a 64 x 64 LDS tile (tails masked, the norm backward on the
 //                            load), and the partial sums of dy x rel per (scene, run, face);
-//   nesie_inverted_index     the 3n taps of a scene sorted by seed, ascending tap position 3p + t
+//   launch_inverted_index    the 3n taps of a scene sorted by seed, ascending tap position 3p + t
 //                            inside a seed's run; blend_any_offs_kernel lists the m + 1 run starts;
 //   blend_any_gather_kernel  one wave per (scene, face, seed, block of 256 channels) walks the
 //                            seed's run in that order, skips the other faces' taps, adds
 //                            weight * row and WRITES the d_table row (zeros for an empty run).
 #include "common.h"
+#include "index_sort.h"
 
 namespace nesie {
 
@@ -260,12 +261,11 @@ extern "C" int nesie_blend_conv_backward_any(int b, int c, int m, int n, const f
   else
     hipLaunchKernelGGL(blend_any_rows_kernel<false>, grid, dim3(256), 0, s, c, n, segs, seg_len, dy,
                        rel, z, bnb, dzt, d_wx ? part : (float *)nullptr, b, nruns, ncblk);
-  int st = check_launch(W);
-  if (st) return st;
+  NESIE_LAUNCHED(W);
   if (d_wx)
     hipLaunchKernelGGL(blend_any_wx_kernel, dim3((unsigned)cdiv((long long)segs * c * 3, 256)),
                        dim3(256), 0, s, b * nruns, segs * c * 3, part, d_wx);
-  st = nesie_inverted_index(b, m, (long long)n * 3, idx, order, sources, scratch, stream);
+  const int st = launch_inverted_index(b, m, (long long)n * 3, idx, order, sources, scratch, s);
   if (st) return st;
   hipLaunchKernelGGL(blend_any_offs_kernel, dim3((unsigned)cdiv((long long)n * 3 + 1, 256), b),
                      dim3(256), 0, s, m, n * 3, sources, offs);

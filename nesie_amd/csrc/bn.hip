@@ -30,19 +30,6 @@ __device__ __forceinline__ size_t rb_offset(int b, int c, int c_total, long long
   return group ? ((size_t)b * c_total + c) * (size_t)(p / group) : (size_t)c;
 }
 
-__device__ __forceinline__ float block_sum(float v, float *sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int w = 0; w < BN_BLOCK / 64; ++w) r += sh[w];
-  return r;
-}
-
 // partial[(c * nslice + b * sp + s) * 2 + {0,1}] = sum(x - shift), sum((x - shift)^2)
 __global__ __launch_bounds__(BN_BLOCK) void bn_stats_kernel(
     int c_total, long long p, int sp, const float *__restrict__ x,
@@ -73,8 +60,8 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_stats_kernel(
       a0 += d; a1 += d * d;
     }
   }
-  a0 = block_sum(a0, sh);
-  a1 = block_sum(a1, sh);
+  a0 = block_sum<BN_BLOCK>(a0, sh);
+  a1 = block_sum<BN_BLOCK>(a1, sh);
   if (threadIdx.x == 0) {
     const size_t o = ((size_t)c * (gridDim.z * sp) + (size_t)b * sp + s) * 2;
     partial[o] = a0; partial[o + 1] = a1;
@@ -94,12 +81,6 @@ struct BnFwdFin {
   float *coef;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // -> sh[0] = scale, sh[1] = bias (valid for every thread after the barrier inside)
 __device__ __forceinline__ void bn_fwd_finalize(const BnFwdFin &f, int c, bool writer, float *sh) {
   if (threadIdx.x < 64) {
@@ -108,8 +89,8 @@ __device__ __forceinline__ void bn_fwd_finalize(const BnFwdFin &f, int c, bool w
       s0 += (double)f.partial[((size_t)c * f.nslice + i) * 2];
       s1 += (double)f.partial[((size_t)c * f.nslice + i) * 2 + 1];
     }
-    s0 = wave_sum_f64(s0);
-    s1 = wave_sum_f64(s1);
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
     if (threadIdx.x == 0) {
       // sums are taken about the channel's first element (no shift when the producer of the
       // partials had no such element at hand: f.x == NULL)
@@ -267,8 +248,8 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_reduce_kernel(
       a0 += g; a1 += g * ((v - mean) * invstd);
     }
   }
-  a0 = block_sum(a0, sh);
-  a1 = block_sum(a1, sh);
+  a0 = block_sum<BN_BLOCK>(a0, sh);
+  a1 = block_sum<BN_BLOCK>(a1, sh);
   if (threadIdx.x == 0) {
     const size_t o = ((size_t)c * (gridDim.z * sp) + (size_t)b * sp + s) * 2;
     partial[o] = a0; partial[o + 1] = a1;
@@ -290,8 +271,8 @@ __device__ __forceinline__ void bn_bwd_finalize(const BnBwdFin &f, int c, bool w
       s0 += (double)f.partial[((size_t)c * f.nslice + i) * 2];
       s1 += (double)f.partial[((size_t)c * f.nslice + i) * 2 + 1];
     }
-    s0 = wave_sum_f64(s0);
-    s1 = wave_sum_f64(s1);
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
     if (threadIdx.x == 0) {
       const double g = f.gamma ? (double)f.gamma[c] : 1.0;
       sh[0] = (float)(g * (double)f.save_invstd[(size_t)c * f.istride]);
@@ -431,8 +412,8 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_pool_bwd_reduce_kernel(
       a1 += g * ((xa - mean) * invstd);
     }
   }
-  a0 = block_sum(a0, sh);
-  a1 = block_sum(a1, sh);
+  a0 = block_sum<BN_BLOCK>(a0, sh);
+  a1 = block_sum<BN_BLOCK>(a1, sh);
   if (threadIdx.x == 0) {
     const size_t o = ((size_t)c * (gridDim.z * gridDim.x) + (size_t)b * gridDim.x + s) * 2;
     partial[o] = a0; partial[o + 1] = a1;

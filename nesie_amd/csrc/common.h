@@ -31,7 +31,16 @@ inline int check_launch(const char *what) {
     }                                                               \
   } while (0)
 
+// after a launch: return its error from the enclosing launcher, go on when there is none
+#define NESIE_LAUNCHED(what)                        \
+  do {                                              \
+    const int e_ = nesie::check_launch(what);       \
+    if (e_ != NESIE_OK) return e_;                  \
+  } while (0)
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // true when a tensor of this size should be streamed with non-temporal accesses (bn.hip): the norm
 // and pooling passes ask; the blend stores (same-box A/B: neutral) and the norm statistics do not
@@ -68,6 +77,31 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     v = o > v ? o : v;
   }
   return v;
+}
+
+// Sum across the 64 lanes of a wave (float, double, int), result in every lane: the xor butterfly,
+// offsets 32 down to 1 -- a fixed order, so a float sum is reproducible.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// Sum over a workgroup of BLOCK threads, result in every thread: wave_sum, then the waves' sums
+// in ascending wave order.  sh: BLOCK / 64 floats of LDS; the barrier in front lets a caller hand
+// in the same sh for one sum after another.
+template <int BLOCK>
+__device__ __forceinline__ float block_sum(float v, float *sh) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int w = 0; w < BLOCK / 64; ++w) t += sh[w];
+  return t;
 }
 
 // ---- DPP helpers for reductions inside a row of <= 16 lanes (no LDS, full rate)

@@ -66,12 +66,11 @@ __device__ __forceinline__ float fl_term(float x, bool pos, float gamma, float a
 
 // sum over the workgroup, the same bits in every run; valid in thread 0
 __device__ __forceinline__ float fl_block_sum(float v) {
-  __shared__ float wave_sum[FL_BLOCK / 64];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __shared__ float sh[FL_BLOCK / 64];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
-  return (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 template <bool VEC>
@@ -158,7 +157,6 @@ __global__ __launch_bounds__(FL_BLOCK) void focal_finish_kernel(
   }
 }
 
-static inline bool fl_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // NESIE_OK with `go` = whether there is anything to launch
 static int fl_check(const char *W, int n, int c, const float *x, const long long *target,
@@ -184,8 +182,8 @@ static int fl_check(const char *W, int n, int c, const float *x, const long long
 }
 
 static inline bool fl_vec(const fl_problem &q, const void *a, const void *b) {
-  return fl_aligned16(q.x) && fl_aligned16(a) && fl_aligned16(b) &&
-         (q.sw_mode != 2 || fl_aligned16(q.sample_weight));
+  return aligned16(q.x) && aligned16(a) && aligned16(b) &&
+         (q.sw_mode != 2 || aligned16(q.sample_weight));
 }
 
 #define FL_LAUNCH(MODE, VEC, GRID, ...)                                                            \

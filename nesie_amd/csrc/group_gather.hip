@@ -176,10 +176,8 @@ __global__ __launch_bounds__(GG_BLOCK) void group_bwd_csr_kernel(
       const float w2 = wb ? wb[col2] : 1.f;
 #pragma unroll
       for (int i = 0; i < GG_CH; ++i) {
-        float t = (in && i < cend) ? __fmul_rn(gbase[(size_t)i * ncols + col2 / ediv], w2) : 0.f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-        extra[i] += t;
+        const float t = (in && i < cend) ? __fmul_rn(gbase[(size_t)i * ncols + col2 / ediv], w2) : 0.f;
+        extra[i] += wave_sum(t);
       }
       if (m != ~0ull) break;                               // the run ended inside this trip
     }
@@ -332,10 +330,7 @@ __global__ __launch_bounds__(GR_BLOCK) void group_bwd_csr_rows_kernel(
       for (int i = 0; i < CH; ++i) acc[i] += __fmul_rn(g[i * ncols4], w);
     }
 #pragma unroll
-    for (int i = 0; i < CH; ++i) {
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) acc[i] += __shfl_xor(acc[i], off, 64);
-    }
+    for (int i = 0; i < CH; ++i) acc[i] = wave_sum(acc[i]);
     if (lane == 0) {
 #pragma unroll
       for (int i = 0; i < CH; ++i)
@@ -385,164 +380,6 @@ static bool launch_group_bwd_csr_rows(int b, int c, int n, long long e_total, lo
   else { if (ch == 8) GRL(8, 3); else if (ch == 4) GRL(4, 3); else if (ch == 2) GRL(2, 3); else GRL(1, 3); }
 #undef GRL
   return true;
-}
-
-// Inverted index of idx[b][0..e_total) over n source points, one workgroup per scene: LDS
-// histogram (integer ds_add), exclusive scan, then each column takes the next free slot of its
-// point's run (returning ds_add).  Built on the side stream with the ball query: 8 workgroups,
-// tens of microseconds.  The slots are claimed in arrival order into `scratch`; a second pass
-// ranks every entry inside its run (runs are short: M ns / N on average), so `order` lists each
-// run in ascending column order and the segmented sums of the backward are reproducible.
-constexpr int II_BLOCK = 1024;
-constexpr int II_WINDOW = 8192;     // source points per workgroup (LDS histogram + cursor)
-
-// Any n (round 5): workgroup (scene, window w) owns the source points [w * II_WINDOW, + II_WINDOW):
-// it first counts the entries that belong to EARLIER windows (that many positions of order / srcs lie
-// in front of its own), then sorts its own entries as before.  Every window reads the whole index
-// row, so the cost grows with the window count -- 5 windows at 40 000 points; the step itself only
-// ever inverts indices over <= 2 048 points (the 40 000-point level carries no feature gradient).
-__global__ __launch_bounds__(II_BLOCK) void inverted_index_kernel(
-    int n, int e_total, const int *__restrict__ idx, int *__restrict__ order,
-    int *__restrict__ srcs, int *__restrict__ scratch_out) {
-  extern __shared__ int lds[];  // cursor[bins]; scan scratch [II_BLOCK]; base counter
-  const int lo_pt = blockIdx.y * II_WINDOW;
-  const int bins = n - lo_pt < II_WINDOW ? n - lo_pt : II_WINDOW;
-  int *cur = lds, *scratch = lds + bins, *before = scratch + II_BLOCK;
-  const int bi = blockIdx.x, tid = threadIdx.x;
-  const int *ix = idx + (size_t)bi * e_total;
-  for (int j = tid; j < bins; j += II_BLOCK) cur[j] = 0;
-  if (tid == 0) *before = 0;
-  __syncthreads();
-  int mine_before = 0;
-  for (int e = tid; e < e_total; e += II_BLOCK) {
-    int s = ix[e];
-    s = s < 0 ? 0 : (s >= n ? n - 1 : s);
-    if (s < lo_pt) ++mine_before;
-    else if (s < lo_pt + bins) atomicAdd(&cur[s - lo_pt], 1);
-  }
-  if (lo_pt > 0) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine_before += __shfl_xor(mine_before, off, 64);
-    if ((tid & 63) == 0 && mine_before) atomicAdd(before, mine_before);
-  }
-  __syncthreads();
-  const int base = *before;
-  // exclusive scan over the bins: each thread owns a contiguous chunk
-  const int per = (bins + II_BLOCK - 1) / II_BLOCK;
-  const int lo = tid * per, hi = lo + per < bins ? lo + per : bins;
-  int sum = 0;
-  for (int j = lo; j < hi; ++j) sum += cur[j];
-  scratch[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < II_BLOCK; d <<= 1) {
-    const int v = tid >= d ? scratch[tid - d] : 0;
-    __syncthreads();
-    scratch[tid] += v;
-    __syncthreads();
-  }
-  int run = base + scratch[tid] - sum;  // first position of this chunk
-  for (int j = lo; j < hi; ++j) {
-    const int cnt = cur[j];
-    cur[j] = run;  // becomes the cursor of point lo_pt + j
-    run += cnt;
-  }
-  __syncthreads();
-  int *ord = order + (size_t)bi * e_total;
-  int *sr = srcs + (size_t)bi * e_total;
-  int *tmp = scratch_out + (size_t)bi * e_total;
-  for (int e = tid; e < e_total; e += II_BLOCK) {
-    int s = ix[e];
-    s = s < 0 ? 0 : (s >= n ? n - 1 : s);
-    if (s >= lo_pt && s < lo_pt + bins) tmp[atomicAdd(&cur[s - lo_pt], 1)] = e;
-  }
-  __syncthreads();   // cur[j] is now the END of run j; run j starts where run j - 1 ends (run 0: at base)
-  const int total = cur[bins - 1];
-  for (int i = base + tid; i < total; i += II_BLOCK) {
-    const int e = tmp[i];
-    int s = ix[e];
-    s = (s < 0 ? 0 : (s >= n ? n - 1 : s)) - lo_pt;
-    sr[i] = s + lo_pt;
-    const int lo_s = s > 0 ? cur[s - 1] : base, hi_s = cur[s];
-    int rank = 0;
-    for (int k = lo_s; k < hi_s; ++k) rank += tmp[k] < e ? 1 : 0;
-    ord[lo_s + rank] = e;
-  }
-}
-
-// The same index by a STABLE counting sort (n <= II_STABLE_N bins): no ranking pass.  Wave w of the
-// 16 owns a contiguous range of entries and keeps its own histogram row cnt[w][.] in LDS; after the
-// scan cnt[w][s] is where wave w's first entry of bin s goes (bin-major, wave-minor), and the wave
-// places its entries 64 at a time in ascending order: the lanes that hold the same bin find each
-// other with a ballot per distinct bin of the round and take consecutive positions in lane order.
-// The result is `order` ascending inside every run by construction -- what the ranking pass of
-// inverted_index_kernel computes in time quadratic in the run length.
-constexpr int II_STABLE_N = 2048, II_WAVES = II_BLOCK / 64;
-
-__global__ __launch_bounds__(II_BLOCK) void inverted_index_stable_kernel(
-    int n, int e_total, const int *__restrict__ idx, int *__restrict__ order,
-    int *__restrict__ srcs) {
-  extern __shared__ int lds[];                       // cnt[II_WAVES][n], then scan scratch [II_BLOCK]
-  int *cnt = lds, *scratch = lds + II_WAVES * n;
-  const int bi = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int *ix = idx + (size_t)bi * e_total;
-  for (int j = tid; j < II_WAVES * n; j += II_BLOCK) cnt[j] = 0;
-  __syncthreads();
-  const int per = ((e_total + II_WAVES - 1) / II_WAVES + 63) / 64 * 64;   // entries per wave, whole rounds
-  const int e0 = wave * per, e1 = e0 + per < e_total ? e0 + per : e_total;
-  int *mine = cnt + wave * n;
-  for (int e = e0 + lane; e < e1; e += 64) {
-    int s = ix[e];
-    s = s < 0 ? 0 : (s >= n ? n - 1 : s);
-    atomicAdd(&mine[s], 1);
-  }
-  __syncthreads();
-  // totals per bin -> exclusive scan over the bins -> per-(wave, bin) start positions
-  const int bper = (n + II_BLOCK - 1) / II_BLOCK;    // bins per thread (contiguous)
-  const int b0 = tid * bper, b1 = b0 + bper < n ? b0 + bper : n;
-  int sum = 0;
-  for (int sbin = b0; sbin < b1; ++sbin)
-    for (int w = 0; w < II_WAVES; ++w) sum += cnt[w * n + sbin];
-  scratch[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < II_BLOCK; d <<= 1) {
-    const int v = tid >= d ? scratch[tid - d] : 0;
-    __syncthreads();
-    scratch[tid] += v;
-    __syncthreads();
-  }
-  int run = scratch[tid] - sum;                      // first position of this thread's first bin
-  for (int sbin = b0; sbin < b1; ++sbin)
-    for (int w = 0; w < II_WAVES; ++w) {
-      const int c = cnt[w * n + sbin];
-      cnt[w * n + sbin] = run;
-      run += c;
-    }
-  __syncthreads();
-  int *ord = order + (size_t)bi * e_total;
-  int *sr = srcs + (size_t)bi * e_total;
-  volatile int *cur = mine;                          // this wave's cursors (only this wave touches them)
-  for (int base = e0; base < e1; base += 64) {
-    const int e = base + lane;
-    const bool live = e < e1;
-    int s = live ? ix[e] : 0;
-    s = s < 0 ? 0 : (s >= n ? n - 1 : s);
-    unsigned long long todo = __ballot(live);
-    while (todo) {                                   // one trip per distinct bin of the round
-      const int leader = __builtin_ctzll(todo);
-      const int s0 = __builtin_amdgcn_readlane(s, leader);
-      const unsigned long long mask = __ballot(live && s == s0);
-      const int start = cur[s0];
-      if (live && s == s0) {
-        const int pos = start + __popcll(mask & ((1ull << lane) - 1ull));
-        ord[pos] = e;
-        sr[pos] = s0;
-      }
-      if (lane == leader) cur[s0] = start + __popcll(mask);
-      __builtin_amdgcn_wave_barrier();
-      todo &= ~mask;
-    }
-  }
 }
 
 // channels 0..2 of QueryAndGroup's output: (xyz[idx] - centre) (/ radius), straight from the
@@ -734,8 +571,12 @@ extern "C" int nesie_query_and_group_backward_csr(int b, int c, int n, int npoin
   NESIE_REQUIRE(b >= 0 && c >= 1 && n >= 0 && npoints >= 0 && nsample >= 0, W);
   const long long e_total = (long long)npoints * nsample;
   if (b == 0 || n == 0) return NESIE_OK;
-  NESIE_REQUIRE(grad_out && order && sources && grad_features, W);
-  if (e_total == 0) return NESIE_OK;
+  NESIE_REQUIRE(grad_features, W);
+  if (e_total == 0) {                                  // an empty index: every point's sum is empty
+    zero_fill(grad_features, (long long)b * c * n, (hipStream_t)stream);
+    return check_launch(W);
+  }
+  NESIE_REQUIRE(grad_out && order && sources, W);
   NESIE_REQUIRE(e_total < (1ll << 31) && b <= 65535 && cdiv(c, GG_CH) <= 65535, W);
   if (launch_group_bwd_csr_rows(b, c, n, e_total, (long long)(3 + c) * e_total, 1, grad_out + 3 * e_total, nullptr,
                                 order, sources, grad_features, (hipStream_t)stream))
@@ -750,15 +591,20 @@ extern "C" int nesie_query_and_group_backward_csr(int b, int c, int n, int npoin
 
 // group_points / gather_points backward through an inverted index of idx (nesie_inverted_index):
 // what nesie_group_points_backward adds with float atomics (LDS or HBM), in an order fixed by the
-// index alone.  grad_points must be zero on entry.
+// index alone.  grad_points is WRITTEN in full, whatever it held (zeros for an empty index).
 extern "C" int nesie_group_points_backward_csr(int b, int c, int n, int npoints, int nsample,
                                                const float *grad_out, const int *order,
                                                const int *sources, float *grad_points, void *stream) {
   const char *W = "group_points_backward_csr";
   NESIE_REQUIRE(b >= 0 && c >= 0 && n >= 0 && npoints >= 0 && nsample >= 0, W);
   const long long e_total = (long long)npoints * nsample;
-  if (b == 0 || n == 0 || c == 0 || e_total == 0) return NESIE_OK;
-  NESIE_REQUIRE(grad_out && order && sources && grad_points, W);
+  if (b == 0 || n == 0 || c == 0) return NESIE_OK;
+  NESIE_REQUIRE(grad_points, W);
+  if (e_total == 0) {
+    zero_fill(grad_points, (long long)b * c * n, (hipStream_t)stream);
+    return check_launch(W);
+  }
+  NESIE_REQUIRE(grad_out && order && sources, W);
   NESIE_REQUIRE(e_total < (1ll << 31) && b <= 65535 && cdiv(c, GG_CH) <= 65535, W);
   if (launch_group_bwd_csr_rows(b, c, n, e_total, (long long)c * e_total, 1, grad_out, nullptr, order, sources,
                                 grad_points, (hipStream_t)stream))
@@ -768,39 +614,6 @@ extern "C" int nesie_group_points_backward_csr(int b, int c, int n, int npoints,
                      dim3(GG_BLOCK), 0, (hipStream_t)stream, c, n, (int)e_total, (long long)c * e_total, 1,
                      grad_out, (const float *)nullptr, order, sources, grad_points);
   return check_launch(W);
-}
-
-namespace nesie {
-int launch_inverted_index(int b, int n, long long e_total, const int *idx, int *order, int *sources,
-                          int *scratch, hipStream_t s) {
-  const char *W = "inverted_index";
-  NESIE_REQUIRE(b >= 0 && n >= 1 && e_total >= 0 && e_total < (1ll << 31), W);
-  if (b == 0) return NESIE_OK;
-  NESIE_REQUIRE(idx && order && sources && scratch, W);
-  if (n <= II_STABLE_N) {               // stable counting sort: ascending runs without a ranking pass
-    const size_t lds = ((size_t)II_WAVES * n + II_BLOCK) * sizeof(int);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void *)inverted_index_stable_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)II_WAVES * II_STABLE_N + II_BLOCK) * sizeof(int)));
-      attr = true;
-    }
-    hipLaunchKernelGGL(inverted_index_stable_kernel, dim3(b), dim3(II_BLOCK), lds, s, n, (int)e_total, idx,
-                       order, sources);
-    return check_launch(W);
-  }
-  const int windows = cdiv(n, II_WINDOW);
-  NESIE_REQUIRE(windows <= 65535, W);
-  const size_t lds = ((size_t)(n < II_WINDOW ? n : II_WINDOW) + II_BLOCK + 1) * sizeof(int);
-  hipLaunchKernelGGL(inverted_index_kernel, dim3(b, windows), dim3(II_BLOCK), lds, s, n, (int)e_total, idx, order,
-                     sources, scratch);
-  return check_launch(W);
-}
-}  // namespace nesie
-
-extern "C" int nesie_inverted_index(int b, int n, long long e_total, const int *idx, int *order,
-                                    int *sources, int *scratch, void *stream) {
-  return launch_inverted_index(b, n, e_total, idx, order, sources, scratch, (hipStream_t)stream);
 }
 
 extern "C" int nesie_three_interpolate_grad_csr(int b, int c, int n, int m, const float *grad_out,

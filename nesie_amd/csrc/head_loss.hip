@@ -18,19 +18,6 @@ namespace nesie {
 constexpr int HL_BLOCK = 1024;
 constexpr int HL_MAXC = 32;      // classes
 
-__device__ __forceinline__ float hl_block_sum(float v, float *sh) {
-  // fixed-order tree over the block: lanes by DPP-free shuffles, waves through LDS
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int w = 0; w < HL_BLOCK / 64; ++w) t += sh[w];
-  return t;
-}
-
 __device__ __forceinline__ int hl_block_count(int v, int *sh) {
   __syncthreads();
   if (threadIdx.x == 0) *sh = 0;
@@ -304,10 +291,7 @@ __global__ __launch_bounds__(HL_PB) void head_loss_kernel(const HeadLoss a) {
   }
   float v[7] = {l_obj, l_sem, l_c, l_surf, l_iou, l_qfl, l_side};
 #pragma unroll
-  for (int i = 0; i < 7; ++i) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-  }
+  for (int i = 0; i < 7; ++i) v[i] = wave_sum(v[i]);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) a.partial[(size_t)blockIdx.x * 8 + i] = v[i];
@@ -456,10 +440,7 @@ __global__ __launch_bounds__(HL_PB) void saqe_extra_kernel(const SaqeExtra a) {
   }
   float v[4] = {l0, l1, l2, l3};
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-  }
+  for (int i = 0; i < 4; ++i) v[i] = wave_sum(v[i]);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) a.partial[(size_t)blockIdx.x * 4 + i] = v[i];

@@ -12,6 +12,7 @@
 // float compares with a +inf start (1e40 rounds to +inf on output), so floats
 // are used here.  Ties keep the earlier index in the better slot (strict <).
 #include "common.h"
+#include "index_sort.h"
 #include <math.h>
 
 namespace nesie {
@@ -641,7 +642,7 @@ constexpr int SI_MAX_BINS = 2048;                      // seeds + 1 (LDS: 16 his
 __global__ __launch_bounds__(SI_BLOCK) void blend_slot_index_kernel(
     int m, int groups_per_face, int nchunk, const int *__restrict__ slot_seed,
     int *__restrict__ order, int *__restrict__ offs) {
-  extern __shared__ int si_lds[];                      // cnt[SI_WAVES][m], then scan scratch [SI_BLOCK]
+  extern __shared__ int si_lds[];                      // cnt[SI_WAVES][m], then scan scratch [SI_WAVES]
   int *cnt = si_lds, *scratch = si_lds + SI_WAVES * m;
   const int face = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -665,32 +666,7 @@ __global__ __launch_bounds__(SI_BLOCK) void blend_slot_index_kernel(
   for (int u = 0; u < GPW; ++u)
     if (sv[u] >= 0) atomicAdd(&mine[sv[u]], 1);        // (distinct bins inside a group)
   __syncthreads();
-  // totals per bin -> exclusive scan over the bins -> per-(wave, bin) start positions
-  const int bper = (m + SI_BLOCK - 1) / SI_BLOCK;      // bins per thread (contiguous)
-  const int b0 = tid * bper, b1 = b0 + bper < m ? b0 + bper : m;
-  int sum = 0;
-  for (int sbin = b0; sbin < b1; ++sbin)
-    for (int w = 0; w < SI_WAVES; ++w) sum += cnt[w * m + sbin];
-  scratch[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < SI_BLOCK; d <<= 1) {
-    const int v = tid >= d ? scratch[tid - d] : 0;
-    __syncthreads();
-    scratch[tid] += v;
-    __syncthreads();
-  }
-  int *of = offs + ((size_t)face * nchunk + chunk) * (m + 1);
-  int run = scratch[tid] - sum;                        // first position of this thread's first bin
-  for (int sbin = b0; sbin < b1; ++sbin) {
-    of[sbin] = run;
-    for (int w = 0; w < SI_WAVES; ++w) {
-      const int c = cnt[w * m + sbin];
-      cnt[w * m + sbin] = run;
-      run += c;
-    }
-  }
-  if (tid == SI_BLOCK - 1) of[m] = scratch[SI_BLOCK - 1];
-  __syncthreads();
+  counting_sort_starts<SI_BLOCK>(cnt, m, scratch, offs + ((size_t)face * nchunk + chunk) * (m + 1));
   int *ord = order + ((size_t)face * nchunk + chunk) * (SI_GROUPS * BL_SLOTS);
 #pragma unroll
   for (int u = 0; u < GPW; ++u) {                      // groups in order: the stable placement
@@ -990,11 +966,11 @@ static int blend_conv_backward_impl(const char *W, int b, int c, int m, int n, c
     if (c == 64) LS(1); else if (c == 128) LS(2); else if (c == 192) LS(3); else LS(4);
 #undef LS
     {
-      const size_t lds = ((size_t)SI_WAVES * m + SI_BLOCK) * sizeof(int);
+      const size_t lds = ((size_t)SI_WAVES * m + SI_WAVES) * sizeof(int);
       static bool attr = false;
       if (!attr) {
         (void)hipFuncSetAttribute((const void *)blend_slot_index_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(((size_t)SI_WAVES * SI_MAX_BINS + SI_BLOCK) * sizeof(int)));
+                                  (int)(((size_t)SI_WAVES * SI_MAX_BINS + SI_WAVES) * sizeof(int)));
         attr = true;
       }
       hipLaunchKernelGGL(blend_slot_index_kernel, dim3((unsigned)(b * segs * nchunk)), dim3(SI_BLOCK), lds, s,

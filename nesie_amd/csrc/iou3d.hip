@@ -7,11 +7,11 @@
 // plus its sort_vertices launch.  One thread owns one (prediction, target) pair and walks
 // the same formulas in the same order: corners, 4x4 edge intersections with the
 // t,u in (0,1) test and the `num + 1e-8` re-division, corner-in-box tests with 1e-6
-// slack, mean-centred angular sort (sort_device.h), shoelace area, z overlap.
+// slack, mean-centred angular sort (vertex_order.h), shoelace area, z overlap.
 // Gradients w.r.t. the 7 parameters of the FIRST box are carried forward as dual numbers
 // (masks and the vertex order are piecewise constant, exactly as autograd treats them);
 // the second box is a constant (targets never require grad on this path).
-#include "sort_device.h"
+#include "vertex_order.h"
 #include <math.h>
 
 namespace nesie {

@@ -589,9 +589,7 @@ __global__ __launch_bounds__(256) void k4_moments_kernel(int nb, long long p, lo
   }
 #pragma unroll
   for (int u = 0; u < 20; ++u) {
-    double t = all[u];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    const double t = wave_sum(all[u]);
     if (lane == 0) red[wave][u] = t;
   }
   __syncthreads();
@@ -623,17 +621,13 @@ __global__ __launch_bounds__(256) void k4_wgrad_finish_kernel(int nslots, const 
   }
 #pragma unroll
   for (int u = 0; u < 20; ++u) {
-    double t = m[u];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    const double t = wave_sum(m[u]);
     if (lane == 0) red[wave][u] = t;
   }
   if (wave == 0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      double t = g[j];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+      const double t = wave_sum(g[j]);
       if (lane == 0) gs[j] = t;
     }
   }
@@ -667,9 +661,7 @@ __global__ __launch_bounds__(256) void k4_stat_finalize_kernel(double n, const d
   for (int u = 0; u < 20; ++u) m[u] = mom_part[(size_t)tid * 20 + u];
 #pragma unroll
   for (int u = 0; u < 20; ++u) {
-    double t = m[u];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    const double t = wave_sum(m[u]);
     if (lane == 0) red[wave][u] = t;
   }
   __syncthreads();

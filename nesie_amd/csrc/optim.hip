@@ -23,8 +23,7 @@ __global__ __launch_bounds__(OPT_BLOCK) void sumsq_partials_kernel(long long n, 
   const long long lo = (long long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
   float s = 0.f;
   for (long long i = lo + threadIdx.x; i < hi; i += OPT_BLOCK) s += g[i] * g[i];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -46,8 +45,7 @@ __global__ __launch_bounds__(OPT_BLOCK) void adamw_clip_kernel(
   // total squared norm: OPT_PARTS partials, 4 per thread, then the block tree (same everywhere)
   float s = 0.f;
   for (int i = threadIdx.x; i < OPT_PARTS; i += OPT_BLOCK) s += part[i];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

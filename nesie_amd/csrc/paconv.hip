@@ -335,7 +335,6 @@ static int pa_check(const char *W, int b, int n0, int n1, int k, int m, int o, p
   return NESIE_OK;
 }
 
-static inline bool pa_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static inline size_t pa_round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace nesie
@@ -352,7 +351,7 @@ extern "C" int nesie_assign_score_withk_forward(int b, int n0, int n1, int k, in
   const int st = pa_check(W, b, n0, n1, k, m, o, &z, &go);
   if (st || !go) return st;
   NESIE_REQUIRE(points && centers && scores && knn_idx && output, W);
-  const bool vec = o % 4 == 0 && pa_aligned16(points) && pa_aligned16(centers);
+  const bool vec = o % 4 == 0 && aligned16(points) && aligned16(centers);
   const int per = PA_UNITS * (vec ? 4 : 1);
   const int ochunks = cdiv(o, per);
   const long long grid = (long long)b * n1 * ochunks;   // <= elements of the output
@@ -392,7 +391,7 @@ extern "C" int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, i
   int st = pa_check(W, b, n0, n1, k, m, o, &z, &go);
   if (st || !go) return st;
   if (!grad_points && !grad_centers && !grad_scores) return NESIE_OK;
-  NESIE_REQUIRE(grad_out && knn_idx && workspace && pa_aligned16(workspace), W);
+  NESIE_REQUIRE(grad_out && knn_idx && workspace && aligned16(workspace), W);
   NESIE_REQUIRE(workspace_bytes >= nesie_assign_score_withk_backward_workspace_bytes(b, n0, n1, k, m, o), W);
   NESIE_REQUIRE(!grad_scores || (points && centers), W);
   NESIE_REQUIRE(!(grad_points || grad_centers) || scores, W);
@@ -413,21 +412,21 @@ extern "C" int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, i
   NESIE_REQUIRE(tgrid < (1ll << 31), W);
   hipLaunchKernelGGL(paconv_transpose_kernel, dim3((unsigned)tgrid), dim3(PA_BLOCK), 0, s, o, pairs,
                      tiles_o, tiles_e, grad_out, gT);
-  if ((st = check_launch(W))) return st;
+  NESIE_LAUNCHED(W);
 
   if (grad_scores) {
-    const int vec = o % 4 == 0 && pa_aligned16(points) && pa_aligned16(centers);
+    const int vec = o % 4 == 0 && aligned16(points) && aligned16(centers);
     hipLaunchKernelGGL(paconv_grad_scores_kernel, dim3((unsigned)(b * n1)), dim3(PA_BLOCK), 0, s, n0, n1,
                        k, m, o, vec, points, centers, gT, knn_idx, grad_scores);
-    if ((st = check_launch(W))) return st;
+    NESIE_LAUNCHED(W);
   }
   if (!grad_points && !grad_centers) return NESIE_OK;
 
   hipLaunchKernelGGL(paconv_prep_kernel, dim3((unsigned)cdiv(z.pairs, PA_BLOCK)), dim3(PA_BLOCK), 0, s,
                      z.pairs, k, n0, knn_idx, idx32, cn32);
-  if ((st = check_launch(W))) return st;
-  const bool vec = o % 4 == 0 && (!grad_points || pa_aligned16(grad_points)) &&
-                   (!grad_centers || pa_aligned16(grad_centers));
+  NESIE_LAUNCHED(W);
+  const bool vec = o % 4 == 0 && (!grad_points || aligned16(grad_points)) &&
+                   (!grad_centers || aligned16(grad_centers));
   const int total = (int)((long long)m * o / (vec ? 4 : 1));
   const int chunks = cdiv(total, PA_BLOCK * PA_SR);
   const long long sgrid = (long long)b * n0 * chunks;   // <= elements of grad_points
@@ -439,13 +438,13 @@ extern "C" int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, i
     if ((st = nesie_inverted_index(b, n0 + 1, pairs, idx32, p_order, p_src, p_tmp, stream))) return st;
     if (vec) PA_SCATTER(4, false, pairs, p_order, p_src, grad_points);
     else PA_SCATTER(1, false, pairs, p_order, p_src, grad_points);
-    if ((st = check_launch(W))) return st;
+    NESIE_LAUNCHED(W);
   }
   if (grad_centers) {
     if ((st = nesie_inverted_index(b, n0 + 1, n1, cn32, c_order, c_src, c_tmp, stream))) return st;
     if (vec) PA_SCATTER(4, true, n1, c_order, c_src, grad_centers);
     else PA_SCATTER(1, true, n1, c_order, c_src, grad_centers);
-    if ((st = check_launch(W))) return st;
+    NESIE_LAUNCHED(W);
   }
 #undef PA_SCATTER
   return NESIE_OK;

@@ -31,8 +31,7 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(int nb, int ng, int c,
     s += (v[0] + v[1]) + (v[2] + v[3]);
   }
   for (; e < total; e += 256) s += x[(size_t)(e / p) * bstride + (size_t)ch * p + e % p];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((tid & 63) == 0) part[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) out[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);

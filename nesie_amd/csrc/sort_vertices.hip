@@ -12,7 +12,7 @@
 // Where the reference is undefined -- compare_vertices falls off its end when
 // y1*y2 == 0 in some branches, `pad` is uninitialised when no intersection slot
 // is free -- this kernel returns false / uses M-1, as oracle/nesie_oracle.c does.
-#include "sort_device.h"
+#include "vertex_order.h"
 
 namespace nesie {
 

@@ -5,12 +5,12 @@
 //   phase 1, nesie_spconv_out_sites
 //     sc_in_keys_kernel   key of every input row, `cells` for a row outside the grid (the range
 //                         test comes before the key is formed)
-//     vx_sort             the stable radix sort of voxel.hip -> sorted_keys, sorted_rows
+//     ix_sort             the stable radix sort (index_sort.hip) -> sorted_keys, sorted_rows
 //     sc_mark_kernel      copies the sorted keys out, flags and counts the offending rows
 //                         (outside the grid; every row of an equal-key run after its first)
 //     regular conv        sc_cand_kernel forms the n * K candidate output keys (an impossible
 //                         candidate carries the key `cells` of the output grid and sorts last),
-//                         vx_sort on (key, i * K + k), sc_head_kernel + vx_scan: the scan value
+//                         ix_sort on (key, i * K + k), sc_head_kernel + ix_scan: the scan value
 //                         is the output row; sc_fill_kernel writes it to nbr_t and the head of
 //                         every run writes its out_indices row
 //     submanifold         M = n; sc_subm_nbrt_kernel binary-searches sorted_keys
@@ -38,7 +38,7 @@
 // the product G^T . dOut over the chunk's rows 32 at a time with the same MFMA (K = rows), partial
 // products into scratch; sc_wgrad_sum_kernel adds the partials in ascending chunk order.
 #include "common.h"
-#include "voxel_sort.h"
+#include "index_sort.h"
 
 namespace nesie {
 
@@ -445,13 +445,6 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_wgrad_sum_kernel(long long total,
 }
 
 // ---- host side
-static long long sc_cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
-#define SC_LAUNCHED(W)                      \
-  do {                                      \
-    const int e_ = check_launch(W);         \
-    if (e_ != NESIE_OK) return e_;          \
-  } while (0)
 
 static int sc_geom(const char *W, int batch, const int *shape, const int *ksize, const int *stride,
                    const int *padding, int subm, ScGeom &g) {
@@ -495,9 +488,9 @@ static int sc_geom(const char *W, int batch, const int *shape, const int *ksize,
 static int sc_check_nk(const char *W, long long n, long long kvol) {
   NESIE_REQUIRE(n >= 0, W);
   NESIE_REQUIRE(kvol >= 1, W);
-  if (kvol > SC_MAX_KVOL || n > VX_MAX_N / kvol) {
+  if (kvol > SC_MAX_KVOL || n > IX_MAX_N / kvol) {
     set_error("%s: %lld sites x %lld taps, at most %lld candidates and %d taps", W, n, kvol,
-              VX_MAX_N, SC_MAX_KVOL);
+              IX_MAX_N, SC_MAX_KVOL);
     return NESIE_ERR_UNSUPPORTED;
   }
   return NESIE_OK;
@@ -505,7 +498,7 @@ static int sc_check_nk(const char *W, long long n, long long kvol) {
 
 // scratch: bad[n], then the sort's carve for max(n, n * K) elements (n for a submanifold conv)
 static long long sc_rules_ints(long long n, long long kvol, int subm) {
-  return n + vx_carve(nullptr, subm ? n : n * kvol).ints;
+  return n + ix_carve(nullptr, subm ? n : n * kvol).ints;
 }
 
 }  // namespace nesie
@@ -553,36 +546,36 @@ extern "C" int nesie_spconv_out_sites(long long n, const int *indices, int batch
   int *bad = (int *)workspace;
   void *sort_ws = bad + n;
   const long long nk = n * g.kvol;
-  const unsigned n_grid = (unsigned)sc_cdiv(n, SC_BLOCK), nk_grid = (unsigned)sc_cdiv(nk, SC_BLOCK);
+  const unsigned n_grid = (unsigned)cdiv_ll(n, SC_BLOCK), nk_grid = (unsigned)cdiv_ll(nk, SC_BLOCK);
   if (hipMemsetAsync(counts, 0, 2 * sizeof(int), s) != hipSuccess) return check_launch(W);
 
-  const VxWorkspace w = vx_carve(sort_ws, n);
+  const IxWorkspace w = ix_carve(sort_ws, n);
   hipLaunchKernelGGL(sc_in_keys_kernel, dim3(n_grid), dim3(SC_BLOCK), 0, s, n, g, indices, w.ka,
                      w.ia);
-  SC_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   const unsigned *keys;
   const int *idx;
-  st = vx_sort(W, n, g.cells_in, w, sorted_rows, &keys, &idx, s);
+  st = ix_sort(W, n, g.cells_in, w, sorted_rows, &keys, &idx, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(sc_mark_kernel, dim3(n_grid), dim3(SC_BLOCK), 0, s, n, g.cells_in, keys, idx,
                      sorted_keys, bad, counts, subm ? (int)n : -1);
-  SC_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   if (subm) {
     hipLaunchKernelGGL(sc_subm_nbrt_kernel, dim3(nk_grid), dim3(SC_BLOCK), 0, s, nk, n, g, indices,
                        bad, sorted_keys, sorted_rows, nbr_t);
     return check_launch(W);
   }
   // the first sort's scratch is dead: its results sit in sorted_keys, sorted_rows and bad
-  const VxWorkspace w2 = vx_carve(sort_ws, nk);
+  const IxWorkspace w2 = ix_carve(sort_ws, nk);
   hipLaunchKernelGGL(sc_cand_kernel, dim3(nk_grid), dim3(SC_BLOCK), 0, s, nk, g, indices, bad,
                      w2.ka, w2.ia);
-  SC_LAUNCHED(W);
-  st = vx_sort(W, nk, g.cells_out, w2, nullptr, &keys, &idx, s);
+  NESIE_LAUNCHED(W);
+  st = ix_sort(W, nk, g.cells_out, w2, nullptr, &keys, &idx, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(sc_head_kernel, dim3(nk_grid), dim3(SC_BLOCK), 0, s, nk, g.cells_out, keys,
                      w2.flag);
-  SC_LAUNCHED(W);
-  st = vx_scan(W, nk, w2.flag, w2.flag, w2.sums, counts, nullptr, 0, s);
+  NESIE_LAUNCHED(W);
+  st = ix_scan(W, nk, w2.flag, w2.flag, w2.sums, counts, nullptr, 0, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(sc_fill_kernel, dim3(nk_grid), dim3(SC_BLOCK), 0, s, nk, g, keys, idx,
                      w2.flag, nbr_t, out_indices);
@@ -606,7 +599,7 @@ extern "C" int nesie_spconv_gather_table(long long m, const int *out_indices, lo
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(pair_num, 0, g.kvol * sizeof(int), s) != hipSuccess) return check_launch(W);
   const long long total = m * g.kvol;
-  hipLaunchKernelGGL(sc_table_kernel, dim3((unsigned)sc_cdiv(total, SC_BLOCK)), dim3(SC_BLOCK), 0,
+  hipLaunchKernelGGL(sc_table_kernel, dim3((unsigned)cdiv_ll(total, SC_BLOCK)), dim3(SC_BLOCK), 0,
                      s, total, n, g, subm, out_indices, sorted_keys, sorted_rows, nbr, pair_num);
   return check_launch(W);
 }
@@ -641,13 +634,13 @@ extern "C" int nesie_spconv_gather_gemm(long long rows, long long src_rows, int 
   if (rows == 0) return NESIE_OK;
   NESIE_REQUIRE(weight && table && dst, W);
   NESIE_REQUIRE(src_rows == 0 || src, W);
-  const long long row_tiles = sc_cdiv(rows, SG_TM);
+  const long long row_tiles = cdiv_ll(rows, SG_TM);
   if (row_tiles > 2147483647LL || src_rows > 2147483647LL) {
     set_error("%s: %lld rows from %lld are more than one launch covers", W, rows, src_rows);
     return NESIE_ERR_UNSUPPORTED;
   }
   const int nb = c_dst <= 32 ? 1 : (c_dst <= 64 ? 2 : 4);
-  const long long col_tiles = sc_cdiv(c_dst, 32 * nb);
+  const long long col_tiles = cdiv_ll(c_dst, 32 * nb);
   if (col_tiles > 65535) {
     set_error("%s: %d destination channels are more than one launch covers", W, c_dst);
     return NESIE_ERR_UNSUPPORTED;
@@ -681,13 +674,13 @@ extern "C" int nesie_spconv_wgrad(long long rows, long long src_rows, int kvol, 
   NESIE_REQUIRE(rows >= 0 && src_rows >= 0 && kvol >= 1 && c_in >= 1 && c_out >= 1, W);
   if (rows == 0 || src_rows == 0) return NESIE_OK;
   NESIE_REQUIRE(src && dout && table && dw && workspace, W);
-  const long long tiles = sc_cdiv(c_in, SW_T) * sc_cdiv(c_out, SW_T);
+  const long long tiles = cdiv_ll(c_in, SW_T) * cdiv_ll(c_out, SW_T);
   if (kvol > 65535 || tiles > 65535 || src_rows > 2147483647LL) {
     set_error("%s: %d taps x %lld tiles are more than one launch covers", W, kvol, tiles);
     return NESIE_ERR_UNSUPPORTED;
   }
   const int nchunks = sw_chunks(rows);
-  const long long chunk_rows = sc_cdiv(sc_cdiv(rows, nchunks), SW_RB) * SW_RB;
+  const long long chunk_rows = cdiv_ll(cdiv_ll(rows, nchunks), SW_RB) * SW_RB;
   const bool vec = c_in % 4 == 0 && c_out % 4 == 0 && ((uintptr_t)src & 15) == 0 &&
                    ((uintptr_t)dout & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
@@ -699,9 +692,9 @@ extern "C" int nesie_spconv_wgrad(long long rows, long long src_rows, int kvol, 
   else
     hipLaunchKernelGGL(sc_wgrad_kernel<false>, grid, block, 0, s, rows, src_rows, kvol, c_in,
                        c_out, chunk_rows, nchunks, src, dout, table, partial);
-  SC_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   const long long cc = (long long)c_in * c_out, total = cc * kvol;
-  hipLaunchKernelGGL(sc_wgrad_sum_kernel, dim3((unsigned)sc_cdiv(total, SC_BLOCK)), block, 0, s,
+  hipLaunchKernelGGL(sc_wgrad_sum_kernel, dim3((unsigned)cdiv_ll(total, SC_BLOCK)), block, 0, s,
                      total, cc, nchunks, partial, dw);
   return check_launch(W);
 }

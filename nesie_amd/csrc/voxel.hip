@@ -2,23 +2,9 @@
 // mmdet3d/ops/voxel/src/{voxelization_cpu.cpp, voxelization_cuda.cu, scatter_points_cuda.cu};
 // include/nesie_ops.h states the pinned semantics).
 //
-// One primitive serves the three sorted ops: a STABLE least-significant-digit radix sort of
-// (cell key, point index) pairs, 8 bits a pass, the pass count fixed on the host by the bit length
-// of `cells` (an out-of-range point carries the key `cells` and so sorts last).  A pass is
-//   vx_hist_kernel     one workgroup per tile of VX_SORT_TILE keys: 256 LDS counters, integer LDS
-//                      atomics (a count does not depend on their order), written digit-major
-//                      hist[digit][tile]
-//   vx_scan            exclusive scan of the 256 x tiles counters (below)
-//   vx_scatter_kernel  the same tile again.  A wave owns 256 consecutive keys and takes them 64 at
-//                      a time; a lane finds the lanes of its round with the same digit from eight
-//                      ballots, its rank among them is a popcount, and the wave's running count
-//                      per digit sits in LDS private to the wave (read by all, advanced by the
-//                      highest lane of each group; no atomics assign a slot).  After one barrier a
-//                      thread per digit stacks the four waves on the scanned tile base.  Order
-//                      inside a digit is wave, round, lane = input order: the pass is stable.
-// vx_scan: a two-level exclusive scan of ints for any length -- vx_scan_tiles (VX_SCAN_TILE
-// elements per workgroup, tile totals out), vx_scan_sums (one workgroup walks the totals in chunks
-// of 256 with a carry, so their number is unbounded) and vx_scan_add.
+// One primitive serves the three sorted ops: the stable radix sort of index_sort.hip (ix_sort) on
+// (cell key, point index) pairs; an out-of-range point carries the key `cells` and so sorts last.
+// The scans are ix_scan, the any-length exclusive scan of the same unit.
 //
 // After the sort a cell's points are contiguous in ascending point index and the cells are in key
 // (= lexicographic) order.
@@ -39,12 +25,11 @@
 #include <math.h>
 
 #include "common.h"
-#include "voxel_sort.h"
+#include "index_sort.h"
 
 namespace nesie {
 
 constexpr int VX_BLOCK = 256;
-constexpr int VX_SCAN_TILE = 1024;  // ints per scan workgroup: 256 threads x 4
 constexpr int VX_CT = 256;          // channels one reduce pass holds (4 per lane)
 
 struct VxGrid {
@@ -101,153 +86,6 @@ __global__ __launch_bounds__(VX_BLOCK) void vx_coor_keys_kernel(long long n, int
   const bool ok = a >= 0 && a < d0 && b >= 0 && b < d1 && e >= 0 && e < d2;
   keys[i] = ok ? (unsigned)((a * d1 + b) * d2 + e) : cells;
   idx[i] = (int)i;
-}
-
-// ---- radix sort pass
-__global__ __launch_bounds__(VX_BLOCK) void vx_hist_kernel(long long n, int shift, long long nb,
-                                                           const unsigned *__restrict__ keys,
-                                                           int *__restrict__ hist) {
-  __shared__ int h[256];
-  const int tid = threadIdx.x;
-  h[tid] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * VX_SORT_TILE;
-#pragma unroll
-  for (int k = 0; k < VX_SORT_TILE / VX_BLOCK; ++k) {
-    const long long i = base + k * VX_BLOCK + tid;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1);
-  }
-  __syncthreads();
-  hist[(long long)tid * nb + blockIdx.x] = h[tid];
-}
-
-__global__ __launch_bounds__(VX_BLOCK) void vx_scatter_kernel(
-    long long n, int shift, long long nb, const unsigned *__restrict__ kin,
-    const int *__restrict__ iin, unsigned *__restrict__ kout, int *__restrict__ iout,
-    const int *__restrict__ hist) {
-  constexpr int W = VX_BLOCK / 64, R = VX_SORT_TILE / VX_BLOCK;
-  __shared__ int wcnt[W][256];
-  __shared__ int off[W][256];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int i = tid; i < W * 256; i += VX_BLOCK) (&wcnt[0][0])[i] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * VX_SORT_TILE + w * (R * 64);
-  volatile int *mine = wcnt[w];
-  unsigned key[R];
-  int id[R], rank[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const long long i = base + r * 64 + lane;
-    const bool valid = i < n;
-    key[r] = valid ? kin[i] : 0u;
-    id[r] = valid ? iin[i] : 0;
-    const unsigned d = (key[r] >> shift) & 255u;
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
-    // the wave's count of digit d before this round: every lane of the group reads it, then the
-    // group's highest lane advances it (LDS serves one wave's accesses in program order)
-    const int before = mine[d];
-    rank[r] = before + __popcll(peers & ((1ull << lane) - 1ull));
-    __builtin_amdgcn_wave_barrier();
-    if (valid && (peers >> lane) == 1ull) mine[d] = before + __popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  {
-    int run = hist[(long long)tid * nb + blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-      off[k][tid] = run;
-      run += wcnt[k][tid];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const long long i = base + r * 64 + lane;
-    if (i < n) {
-      const int dst = off[w][(key[r] >> shift) & 255u] + rank[r];
-      kout[dst] = key[r];
-      iout[dst] = id[r];
-    }
-  }
-}
-
-// ---- exclusive scan of ints
-// exclusive prefix of t over the workgroup's 256 threads; total in every thread.  lds: 4 ints.
-__device__ __forceinline__ int vx_block_excl(int t, int *lds, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = t;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
-  if (lane == 63) lds[w] = inc;
-  __syncthreads();
-  int wbase = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < VX_BLOCK / 64; ++k) {
-    const int s = lds[k];
-    if (k < w) wbase += s;
-    total += s;
-  }
-  __syncthreads();
-  return wbase + inc - t;
-}
-
-__global__ __launch_bounds__(VX_BLOCK) void vx_scan_tiles_kernel(long long n,
-                                                                 const int *in, int *out,
-                                                                 int *__restrict__ sums) {
-  __shared__ int lds[VX_BLOCK / 64];
-  const long long i0 = (long long)blockIdx.x * VX_SCAN_TILE + threadIdx.x * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-  int total;
-  int run = vx_block_excl(v[0] + v[1] + v[2] + v[3], lds, total);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (i0 + k < n) out[i0 + k] = run;
-    run += v[k];
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: the tile totals become their exclusive prefix; the grand total goes to *total
-// and, when given, min(total, cap) to *capped
-__global__ __launch_bounds__(VX_BLOCK) void vx_scan_sums_kernel(long long nt, int *__restrict__ sums,
-                                                                int *__restrict__ total_out,
-                                                                int *__restrict__ capped, int cap) {
-  __shared__ int lds[VX_BLOCK / 64];
-  int carry = 0;
-  for (long long b = 0; b < nt; b += VX_BLOCK) {
-    const long long i = b + threadIdx.x;
-    const int v = i < nt ? sums[i] : 0;
-    int total;
-    const int ex = vx_block_excl(v, lds, total);
-    if (i < nt) sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    if (total_out) *total_out = carry;
-    if (capped) *capped = carry < cap ? carry : cap;
-  }
-}
-
-__global__ __launch_bounds__(VX_BLOCK) void vx_scan_add_kernel(long long n, int *__restrict__ out,
-                                                               const int *__restrict__ sums) {
-  const long long i0 = (long long)blockIdx.x * VX_SCAN_TILE + threadIdx.x * 4;
-  const int add = sums[blockIdx.x];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (i0 + k < n) out[i0 + k] += add;
 }
 
 // ---- hard voxelization
@@ -445,39 +283,6 @@ __global__ __launch_bounds__(VX_BLOCK) void vx_backward_max_kernel(
 }
 
 // ---- host side
-static long long vx_cdiv(long long a, long long b) { return (a + b - 1) / b; }
-
-VxWorkspace vx_carve(void *ws, long long n) {
-  VxWorkspace w;
-  w.nb = vx_cdiv(n, VX_SORT_TILE);
-  const long long hist = 256 * w.nb;
-  const long long sums = vx_cdiv(hist > n ? hist : n, VX_SCAN_TILE) + 1;
-  int *p = (int *)ws;
-  w.ka = (unsigned *)p; p += n;
-  w.kb = (unsigned *)p; p += n;
-  w.ia = p; p += n;
-  w.ib = p; p += n;
-  w.flag = p; p += n;
-  w.hist = p; p += hist;
-  w.sums = p; p += sums;
-  w.meta = p; p += 4;
-  w.ints = 5 * n + hist + sums + 4;
-  return w;
-}
-
-int vx_check_n_cells(const char *W, long long n, long long cells) {
-  NESIE_REQUIRE(n >= 0, W);
-  if (cells < 1 || cells >= 2147483648LL) {
-    set_error("%s: %lld cells outside 1 .. 2^31 - 1", W, cells);
-    return NESIE_ERR_UNSUPPORTED;
-  }
-  if (n > VX_MAX_N) {
-    set_error("%s: %lld points, at most %lld", W, n, VX_MAX_N);
-    return NESIE_ERR_UNSUPPORTED;
-  }
-  return NESIE_OK;
-}
-
 // grid[j] = roundf((hi - lo) / vs) in fp32; every grid[j] >= 1 and the product below 2^31
 static int vx_grid(const char *W, const float *voxel_size, const float *coors_range, VxGrid &g,
                    long long &cells) {
@@ -503,68 +308,13 @@ static int vx_grid(const char *W, const float *voxel_size, const float *coors_ra
   return NESIE_OK;
 }
 
-#define VX_LAUNCHED(W)                      \
-  do {                                      \
-    const int e_ = check_launch(W);         \
-    if (e_ != NESIE_OK) return e_;          \
-  } while (0)
-
-// out may alias in.  total_out / capped: see vx_scan_sums_kernel
-int vx_scan(const char *W, long long n, const int *in, int *out, int *sums, int *total_out,
-            int *capped, int cap, hipStream_t s) {
-  const long long nt = vx_cdiv(n, VX_SCAN_TILE);
-  hipLaunchKernelGGL(vx_scan_tiles_kernel, dim3((unsigned)nt), dim3(VX_BLOCK), 0, s, n, in, out,
-                     sums);
-  VX_LAUNCHED(W);
-  hipLaunchKernelGGL(vx_scan_sums_kernel, dim3(1), dim3(VX_BLOCK), 0, s, nt, sums, total_out,
-                     capped, cap);
-  VX_LAUNCHED(W);
-  if (nt > 1) {
-    hipLaunchKernelGGL(vx_scan_add_kernel, dim3((unsigned)nt), dim3(VX_BLOCK), 0, s, n, out, sums);
-    VX_LAUNCHED(W);
-  }
-  return NESIE_OK;
-}
-
-static int vx_passes(long long cells) {  // keys lie in 0 .. cells
-  int bits = 0;
-  while ((cells >> bits) != 0) ++bits;
-  return (bits + 7) / 8;
-}
-
-// sorts (w.ka, w.ia) by key; the sorted keys end in *keys, the indices in *idx (`last_idx` when
-// given receives the indices of the last pass directly)
-int vx_sort(const char *W, long long n, long long cells, const VxWorkspace &w, int *last_idx,
-            const unsigned **keys, const int **idx, hipStream_t s) {
-  const int passes = vx_passes(cells);
-  unsigned *const kbuf[2] = {w.ka, w.kb};
-  int *const ibuf[2] = {w.ia, w.ib};
-  int *iout = w.ia;
-  for (int p = 0; p < passes; ++p) {
-    const int src = p & 1, dst = src ^ 1;
-    const int *iin = iout;
-    iout = (p == passes - 1 && last_idx) ? last_idx : ibuf[dst];
-    hipLaunchKernelGGL(vx_hist_kernel, dim3((unsigned)w.nb), dim3(VX_BLOCK), 0, s, n, 8 * p, w.nb,
-                       kbuf[src], w.hist);
-    VX_LAUNCHED(W);
-    const int e = vx_scan(W, 256 * w.nb, w.hist, w.hist, w.sums, nullptr, nullptr, 0, s);
-    if (e != NESIE_OK) return e;
-    hipLaunchKernelGGL(vx_scatter_kernel, dim3((unsigned)w.nb), dim3(VX_BLOCK), 0, s, n, 8 * p,
-                       w.nb, kbuf[src], iin, kbuf[dst], iout, w.hist);
-    VX_LAUNCHED(W);
-  }
-  *keys = kbuf[passes & 1];
-  *idx = iout;
-  return NESIE_OK;
-}
-
 static int vx_zero_int(const char *W, int *p, hipStream_t s) {
   if (p && hipMemsetAsync(p, 0, sizeof(int), s) != hipSuccess) return check_launch(W);
   return NESIE_OK;
 }
 
 static unsigned vx_wave_grid(long long n) {
-  const long long want = vx_cdiv(n, VX_BLOCK / 64);
+  const long long want = cdiv_ll(n, VX_BLOCK / 64);
   return (unsigned)(want < 16384 ? want : 16384);
 }
 
@@ -585,10 +335,10 @@ extern "C" int nesie_voxel_grid_size(const float *voxel_size, const float *coors
 
 extern "C" int nesie_voxel_workspace_bytes(long long n, long long cells, long long *out) {
   const char *W = "voxel_workspace_bytes";
-  const int st = vx_check_n_cells(W, n, cells);
+  const int st = ix_check_n_cells(W, n, cells);
   if (st != NESIE_OK) return st;
   NESIE_REQUIRE(out, W);
-  *out = vx_carve(nullptr, n).ints * (long long)sizeof(int);
+  *out = ix_carve(nullptr, n).ints * (long long)sizeof(int);
   return NESIE_OK;
 }
 
@@ -600,12 +350,12 @@ extern "C" int nesie_dynamic_voxelize(long long n, int c, const float *points,
   VxGrid g;
   long long cells;
   int st = vx_grid(W, voxel_size, coors_range, g, cells);
-  if (st == NESIE_OK) st = vx_check_n_cells(W, n, cells);
+  if (st == NESIE_OK) st = ix_check_n_cells(W, n, cells);
   if (st != NESIE_OK) return st;
   if (n == 0) return NESIE_OK;
   NESIE_REQUIRE(c >= 3, W);
   NESIE_REQUIRE(points && coors, W);
-  hipLaunchKernelGGL(vx_dynamic_kernel, dim3((unsigned)vx_cdiv(n, VX_BLOCK)), dim3(VX_BLOCK), 0,
+  hipLaunchKernelGGL(vx_dynamic_kernel, dim3((unsigned)cdiv_ll(n, VX_BLOCK)), dim3(VX_BLOCK), 0,
                      (hipStream_t)stream, n, c, g, points, coors);
   return check_launch(W);
 }
@@ -619,26 +369,26 @@ extern "C" int nesie_hard_voxelize(long long n, int c, const float *points, cons
   VxGrid g;
   long long cells;
   int st = vx_grid(W, voxel_size, coors_range, g, cells);
-  if (st == NESIE_OK) st = vx_check_n_cells(W, n, cells);
+  if (st == NESIE_OK) st = ix_check_n_cells(W, n, cells);
   if (st != NESIE_OK) return st;
   NESIE_REQUIRE(voxel_num, W);
   hipStream_t s = (hipStream_t)stream;
   if (n == 0 || c == 0) return vx_zero_int(W, voxel_num, s);
   NESIE_REQUIRE(c >= 3, W);
   NESIE_REQUIRE(points && voxels && coors && num_points_per_voxel && workspace, W);
-  const VxWorkspace w = vx_carve(workspace, n);
-  const unsigned pts_grid = (unsigned)vx_cdiv(n, VX_BLOCK);
+  const IxWorkspace w = ix_carve(workspace, n);
+  const unsigned pts_grid = (unsigned)cdiv_ll(n, VX_BLOCK);
   hipLaunchKernelGGL(vx_point_keys_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, c, g,
                      (unsigned)cells, points, w.ka, w.ia);
-  VX_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   const unsigned *keys;
   const int *idx;
-  st = vx_sort(W, n, cells, w, nullptr, &keys, &idx, s);
+  st = ix_sort(W, n, cells, w, nullptr, &keys, &idx, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(vx_first_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, (unsigned)cells,
                      keys, idx, w.flag);
-  VX_LAUNCHED(W);
-  st = vx_scan(W, n, w.flag, w.flag, w.sums, nullptr, voxel_num, max_voxels, s);
+  NESIE_LAUNCHED(W);
+  st = ix_scan(W, n, w.flag, w.flag, w.sums, nullptr, voxel_num, max_voxels, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(vx_hard_fill_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, c,
                      (unsigned)cells, g.g[0], g.g[1], max_points, max_voxels, keys, idx, w.flag,
@@ -662,30 +412,30 @@ extern "C" int nesie_dynamic_scatter_forward(long long n, int c, const float *fe
       return NESIE_ERR_UNSUPPORTED;
     }
   }
-  int st = vx_check_n_cells(W, n, cells);
+  int st = ix_check_n_cells(W, n, cells);
   if (st != NESIE_OK) return st;
   NESIE_REQUIRE(num_voxels, W);
   hipStream_t s = (hipStream_t)stream;
   if (n == 0 || c == 0) return vx_zero_int(W, num_voxels, s);
   NESIE_REQUIRE(feats && coors && voxel_feats && voxel_coors && coors_map && reduce_count &&
                     order && voxel_start && workspace, W);
-  const VxWorkspace w = vx_carve(workspace, n);
-  const unsigned pts_grid = (unsigned)vx_cdiv(n, VX_BLOCK);
+  const IxWorkspace w = ix_carve(workspace, n);
+  const unsigned pts_grid = (unsigned)cdiv_ll(n, VX_BLOCK);
   hipLaunchKernelGGL(vx_coor_keys_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, dims[0],
                      dims[1], dims[2], (unsigned)cells, coors, w.ka, w.ia);
-  VX_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   const unsigned *keys;
   const int *idx;
-  st = vx_sort(W, n, cells, w, order, &keys, &idx, s);
+  st = ix_sort(W, n, cells, w, order, &keys, &idx, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(vx_head_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, (unsigned)cells,
                      keys, w.flag);
-  VX_LAUNCHED(W);
-  st = vx_scan(W, n, w.flag, w.flag, w.sums, num_voxels, nullptr, 0, s);
+  NESIE_LAUNCHED(W);
+  st = ix_scan(W, n, w.flag, w.flag, w.sums, num_voxels, nullptr, 0, s);
   if (st != NESIE_OK) return st;
   hipLaunchKernelGGL(vx_seg_kernel, dim3(pts_grid), dim3(VX_BLOCK), 0, s, n, (unsigned)cells, keys,
                      order, w.flag, coors, coors_map, voxel_coors, voxel_start, w.meta);
-  VX_LAUNCHED(W);
+  NESIE_LAUNCHED(W);
   const dim3 grid(vx_wave_grid(n)), block(VX_BLOCK);
   if (reduce_type == 0)
     hipLaunchKernelGGL(vx_reduce_kernel<0>, grid, block, 0, s, c, feats, order, voxel_start,
@@ -707,8 +457,8 @@ extern "C" int nesie_dynamic_scatter_backward(long long n, int c, const float *g
                                               float *grad_feats, void *stream) {
   const char *W = "dynamic_scatter_backward";
   NESIE_REQUIRE(n >= 0 && c >= 0 && reduce_type >= 0 && reduce_type <= 2, W);
-  if (n > VX_MAX_N) {
-    set_error("%s: %lld points, at most %lld", W, n, VX_MAX_N);
+  if (n > IX_MAX_N) {
+    set_error("%s: %lld points, at most %lld", W, n, IX_MAX_N);
     return NESIE_ERR_UNSUPPORTED;
   }
   if (n == 0 || c == 0) return NESIE_OK;
@@ -723,7 +473,7 @@ extern "C" int nesie_dynamic_scatter_backward(long long n, int c, const float *g
                        num_voxels, grad_feats);
     return check_launch(W);
   }
-  const long long blocks = vx_cdiv(total, VX_BLOCK);
+  const long long blocks = cdiv_ll(total, VX_BLOCK);
   if (blocks > 2147483647LL) {
     set_error("%s: %lld x %d elements are more than one launch covers", W, n, c);
     return NESIE_ERR_UNSUPPORTED;

@@ -366,19 +366,15 @@ def test_blend_conv_matches_oracle(oracle_kernels, hip_device, k, segs, g, h):
     torch.testing.assert_close(res[0][1].cpu(), x0.grad, rtol=1e-4, atol=2e-3)
 
 
-@pytest.mark.parametrize("k,segs,g,h,hot", [(256, 6, 16, 256, 3), (128, 1, 64, 256, 1), (64, 6, 16, 128, 40)])
-def test_staged_blend_backward_is_reproducible_and_equals_the_atomic_form(hip_device, k, segs, g, h, hot):
-    """nesie_blend_conv_backward_staged with most taps on a few seeds (`hot`): a seed then collects
-    rows from hundreds of 16-query groups, other seeds none at all.  Three evaluations: same bits;
-    against a float64 scatter: rounding only; against the atomic form (the path that
-    set_deterministic(False) selects, zero-filled table): summation order only; rows of seeds
-    without taps are written as zeros into a table that arrives full of NaN."""
+def _staged_against_atomic(hip_device, k, segs, g, h, hot, m=96):
     hip = kernels.backend_for(torch.empty(1, device=hip_device))
+    n = k * segs * g
+    assert kernels.blend_backward_form(h, n // segs, m, True) == 'staged'
+    assert kernels.blend_backward_form(h, n // segs, m, False) == 'atomic'
     prev = hip.set_deterministic(True)
     try:
         gen = torch.Generator().manual_seed(k + h)
-        b, m = 2, 96
-        n = k * segs * g
+        b = 2
         hot_idx = torch.randint(0, hot, (b, n, 3), generator=gen)
         cold_idx = torch.randint(m // 2, m, (b, n, 3), generator=gen)
         idx = torch.where(torch.rand(b, n, 3, generator=gen) < 0.7, hot_idx, cold_idx).int().to(hip_device)
@@ -405,7 +401,8 @@ def test_staged_blend_backward_is_reproducible_and_equals_the_atomic_form(hip_de
                 want[bi, :, s_].index_add_(0, rows.reshape(-1), contrib.reshape(-1, h))
         err = (outs[0][0].double().cpu().view(b, m, segs, h) - want).abs().max().item()
         assert err <= 3e-6 * want.abs().max().item(), err
-        assert float(outs[0][0][:, hot:m // 2].abs().max()) == 0.0          # seeds no tap landed on
+        if hot < m // 2:
+            assert float(outs[0][0][:, hot:m // 2].abs().max()) == 0.0      # seeds no tap landed on
         hip.set_deterministic(False)
         d_table = torch.zeros(b, m, segs * h, device=hip_device)
         d_wx = torch.empty(segs, h, 3, device=hip_device)
@@ -414,6 +411,27 @@ def test_staged_blend_backward_is_reproducible_and_equals_the_atomic_form(hip_de
         assert torch.equal(outs[0][1], d_wx)
     finally:
         hip.set_deterministic(prev)
+
+
+# (132, 1, 16, 64): 132 groups of 16 queries per face = one whole index chunk of 128 and a last one of 4
+@pytest.mark.parametrize("k,segs,g,h,hot", [(256, 6, 16, 256, 3), (128, 1, 64, 256, 1), (64, 6, 16, 128, 40),
+                                            (132, 1, 16, 64, 3)])
+def test_staged_blend_backward_is_reproducible_and_equals_the_atomic_form(hip_device, k, segs, g, h, hot):
+    """nesie_blend_conv_backward_staged with most taps on a few seeds (`hot`): a seed then collects
+    rows from hundreds of 16-query groups, other seeds none at all.  Three evaluations: same bits;
+    against a float64 scatter: rounding only; against the atomic form (the path that
+    set_deterministic(False) selects, zero-filled table): summation order only; rows of seeds
+    without taps are written as zeros into a table that arrives full of NaN."""
+    _staged_against_atomic(hip_device, k, segs, g, h, hot)
+
+
+@pytest.mark.parametrize("m", [1, 1023, 1025, 2047])
+def test_staged_blend_backward_at_the_edges_of_the_seed_index(hip_device, m):
+    """The same three comparisons at c = 64 and one face of 64 queries, over the seed counts at
+    which the slot index's block scan changes shape: one bin in all, the last thread without a
+    bin, two bins for the first threads and none for the last waves, and 2047 seeds, the most the
+    staged form serves (a thread of its 1024 then owns 0, 1 or 2 bins)."""
+    _staged_against_atomic(hip_device, 4, 1, 16, 64, 1, m=m)
 
 
 @pytest.mark.parametrize("mode", ["random", "identical", "disjoint", "aligned"])
@@ -798,15 +816,34 @@ def test_csr_scatter_is_bitwise_reproducible_with_long_runs(hip_device, n, m, ns
     assert err <= 2e-6 * want.abs().max().item(), err
 
 
+def test_csr_backward_of_an_empty_index_writes_zeros(hip_device):
+    """npoints = 0: no entry names any point, so every sum is empty.  Both backward entries write
+    their whole output (the callers allocate it uninitialised): a NaN-filled one comes back zero."""
+    hip = kernels.backend_for(torch.empty(1, device=hip_device))
+    b, c, n, ns = 2, 5, 37, 4
+    order = torch.empty(b, 0, dtype=torch.int32, device=hip_device)
+    sources = torch.empty(b, 0, dtype=torch.int32, device=hip_device)
+    gp = torch.full((b, c, n), float('nan'), device=hip_device)
+    hip.group_points_backward_csr(torch.empty(b, c, 0, ns, device=hip_device), order, sources, gp)
+    assert torch.equal(gp, torch.zeros_like(gp))
+    gf = torch.full((b, c, n), float('nan'), device=hip_device)
+    hip.query_and_group_backward_csr(torch.empty(b, 3 + c, 0, ns, device=hip_device), (b, 0, ns), order,
+                                     sources, gf)
+    assert torch.equal(gf, torch.zeros_like(gf))
+
+
+# the last six: one bin; 0 / 1 and 1 / 2 bins per thread of the block scan with a partial last wave;
+# the last size of the stable kernel and the first of the windowed one; three windows, the last of one bin
 @pytest.mark.parametrize("n,e,b", [(40000, 131072, 2), (8193, 5000, 3), (20000, 70000, 1), (2049, 64, 1),
-                                   (300, 4000, 2)])
+                                   (300, 4000, 2), (1, 64, 1), (1023, 1, 1), (1025, 1000, 2),
+                                   (2048, 70000, 1), (2049, 70000, 1), (16385, 3000, 1)])
 def test_inverted_index_of_any_point_count_is_the_stable_sort(hip_device, n, e, b):
     """nesie_inverted_index beyond 8 192 source points (windows of 8 192 per workgroup, each counting
     the entries of the earlier windows first): (order, sources) = the STABLE sort of the entries by
     source point, exactly -- with a few points in hundreds of entries and points without any."""
     hip = kernels.backend_for(torch.empty(1, device=hip_device))
     g = torch.Generator().manual_seed(n + e)
-    hot = torch.randint(0, 5, (b, e), generator=g) * (n // 5)
+    hot = torch.randint(0, 5, (b, e), generator=g) * (n // 5)         # (n < 5: every hot entry is point 0)
     idx = torch.where(torch.rand(b, e, generator=g) < 0.3, hot, torch.randint(0, n, (b, e), generator=g)).int()
     order, sources = hip.inverted_index(idx.view(b, e, 1).to(hip_device), n)
     torch.cuda.synchronize()
