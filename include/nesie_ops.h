@@ -152,7 +152,9 @@ int nesie_query_and_group_backward(int b, int c, int n, int npoints, int nsample
  * every run is summed by exactly ONE wave (the one that holds its first entry follows it through
  * the next chunks) and written by one lane: no float atomics; grad_features is WRITTEN in full
  * (round 5: a point without entries gets its zero here, the caller need not clear it).  Inside a run the columns are in ascending order (scratch[B, M*ns] holds the
- * arrival-order placement that the second pass ranks), so the sums are bitwise reproducible. */
+ * arrival-order placement that the second pass ranks), so the sums are bitwise reproducible.
+ * An entry of idx outside [0, n) is clamped to the nearest point (0 or n - 1): it sorts, and appears
+ * in sources, as that point.  e_total = 0 is a no-op that writes nothing. */
 int nesie_inverted_index(int b, int n, long long e_total, const int *idx, int *order,
                          int *sources, int *scratch, void *stream);
 /* nesie_group_points_backward / nesie_gather_points_grad_wrapper (nsample = 1) through the same

@@ -32,7 +32,9 @@ int ix_scan(const char *W, long long n, const int *in, int *out, int *sums, int 
 int ix_sort(const char *W, long long n, long long cells, const IxWorkspace &w, int *last_idx,
             const unsigned **keys, const int **idx, hipStream_t s);
 
-// nesie_inverted_index (include/nesie_ops.h) for callers inside the library
+// nesie_inverted_index (include/nesie_ops.h) for callers inside the library.  An entry outside
+// [0, n) is clamped to the nearest point (0 or n - 1) in both kernels: it sorts, and appears in
+// `sources`, as that point.  e_total = 0 is a no-op: nothing is launched or written.
 int launch_inverted_index(int b, int n, long long e_total, const int *idx, int *order, int *sources,
                           int *scratch, hipStream_t s);
 

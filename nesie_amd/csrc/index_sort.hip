@@ -377,7 +377,7 @@ int launch_inverted_index(int b, int n, long long e_total, const int *idx, int *
                           int *scratch, hipStream_t s) {
   const char *W = "inverted_index";
   NESIE_REQUIRE(b >= 0 && n >= 1 && e_total >= 0 && e_total < (1ll << 31), W);
-  if (b == 0) return NESIE_OK;
+  if (b == 0 || e_total == 0) return NESIE_OK;  // nothing to sort: no launch, null tensors allowed
   NESIE_REQUIRE(idx && order && sources && scratch, W);
   if (n <= II_STABLE_N) {               // stable counting sort: ascending runs without a ranking pass
     const size_t lds = ((size_t)II_WAVES * n + II_WAVES) * sizeof(int);

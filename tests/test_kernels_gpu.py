@@ -853,6 +853,43 @@ def test_inverted_index_of_any_point_count_is_the_stable_sort(hip_device, n, e, 
         assert np.array_equal(sources[bi].cpu().numpy(), idx[bi].numpy()[want])
 
 
+@pytest.mark.parametrize("n", [300, 2049])
+def test_inverted_index_clamps_entries_outside_the_points(hip_device, n):
+    """An entry outside [0, n) counts as the nearest point, in the stable kernel (n <= 2048) and in
+    the windowed one alike: (order, sources) = the stable sort of the CLAMPED index, `sources`
+    holding the clamped values."""
+    hip = kernels.backend_for(torch.empty(1, device=hip_device))
+    b, e = 2, 3000
+    g = torch.Generator().manual_seed(n)
+    idx = torch.randint(0, n, (b, e), generator=g).int()
+    stray = torch.tensor([-1, n, n + 7], dtype=torch.int32)
+    where = torch.rand(b, e, generator=g) < 0.1
+    idx[where] = stray[torch.randint(0, 3, (int(where.sum()),), generator=g)]
+    idx[:, 0], idx[:, 1], idx[:, e - 1] = -1, n, n + 7
+    order, sources = hip.inverted_index(idx.view(b, e, 1).to(hip_device), n)
+    torch.cuda.synchronize()
+    for bi in range(b):
+        clamped = np.clip(idx[bi].numpy(), 0, n - 1)
+        want = np.argsort(clamped, kind='stable')
+        assert np.array_equal(order[bi].cpu().numpy(), want.astype(np.int32))
+        assert np.array_equal(sources[bi].cpu().numpy(), clamped[want])
+
+
+@pytest.mark.parametrize("n", [300, 2049])
+def test_inverted_index_of_no_entries_writes_nothing(hip_device, n):
+    """e_total = 0 is a no-op on each side of the 2048 switch: through the wrapper it gives empty
+    tensors, and the entry itself, handed buffers with room, leaves every one of them as it was."""
+    hip = kernels.backend_for(torch.empty(1, device=hip_device))
+    order, sources = hip.inverted_index(torch.empty(2, 0, 1, dtype=torch.int32, device=hip_device), n)
+    assert tuple(order.shape) == (2, 0) and tuple(sources.shape) == (2, 0)
+    idx = torch.zeros(2, 64, dtype=torch.int32, device=hip_device)
+    bufs = [torch.full((2, 64), -77, dtype=torch.int32, device=hip_device) for _ in range(3)]
+    kernels._launch("nesie_inverted_index", idx, 2, n, 0, idx, *bufs)
+    torch.cuda.synchronize()
+    for t in bufs:
+        assert bool((t == -77).all())
+
+
 def test_reference_shaped_backward_calls_are_bitwise_reproducible_by_default(oracle_kernels, hip_device):
     """The drop-in API without any precomputed index (mmdet3d.ops call shapes): the backward of
     grouping_operation, QueryAndGroup, gather_points and three_interpolate -- atomicAdd scatters in

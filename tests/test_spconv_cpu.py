@@ -78,6 +78,34 @@ def test_referee_inverse_is_conv_transpose_at_the_original_sites(ksize, stride, 
     assert torch.allclose(by_tables, R.read_rows(dense, idx), rtol=0, atol=1e-12)
 
 
+def _identical(got, want):
+    return got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got, want)
+
+
+def test_vectorised_rulebook_equals_the_brute_force_exactly():
+    """On the inputs of tests/test_spconv_gpu.py: every (grid, n) of TABLE_CASES under every
+    geometry, and a small draw from the box of the carrying sizes; then this file's geometries,
+    a stride-1 conv without padding and a 1 x 1 x 1 among them."""
+    from tests import test_spconv_gpu as G
+    cases = 0
+    for grid, n in G.TABLE_CASES + [('box40', 4000), ('box64', 4000)]:
+        batch, shape, _, _ = G.GRIDS[grid]
+        rows = G.sites(11, grid, n)
+        for ksize, stride, padding, subm in G.GEOMETRIES.values():
+            want = R.rulebook(rows, batch, shape, ksize, stride, padding, subm)
+            got = R.rulebook_fast(rows, batch, shape, ksize, stride, padding, subm)
+            for g, w in zip(got, want):
+                assert _identical(g, w), (grid, n, ksize, stride, padding, subm)
+            cases += 1
+    assert cases == 50
+    idx, _, _ = _case(1)
+    for ksize, stride, padding, subm in GEOMETRIES:
+        want = R.rulebook(idx, BATCH, SHAPE, ksize, stride, padding, subm)
+        got = R.rulebook_fast(idx, BATCH, SHAPE, ksize, stride, padding, subm)
+        for g, w in zip(got, want):
+            assert _identical(g, w), (ksize, stride, padding, subm)
+
+
 def test_output_size_formulas_equal_torch():
     from nesie_amd.mmdet3d_ops.spconv import ops
     for ksize, stride, padding, subm in GEOMETRIES:

@@ -4,7 +4,9 @@ are bit-identical, the rulebook is cached, forward + backward replay from a grap
 ops feed it end to end (tests/_spconv_ref.py is the referee).
 
 Constants the sizes are chosen around: the sort works on tiles of 1024 keys and the scan on tiles
-of 1024 ints (N one below, at and one above 1024; N * K = 5000 * 27 crosses 132 scan tiles); the
+of 1024 ints (N one below, at and one above 1024; N * K = 5000 * 27 crosses 132 scan tiles; the
+scan's second level takes the tile totals 256 at a time with a carry, which 9710 * 27 candidates
+reach for the flag scan and 38 837 * 27 for the digit counters of the candidate sort); the
 gather-GEMM owns 128 output rows per workgroup (SG_TM) and stages 32 source channels a step
 (SG_KC), with 32 / 64 / 128 destination channels per workgroup; the weight gradient cuts the rows
 into ceil(rows / 512) chunks (SW_CHUNK_ROWS, at most 16) and walks them 32 at a time.
@@ -39,6 +41,8 @@ GRIDS = {
     'p2': (2, (9, 10, 11), (9, 10, 11), None),                       # 1980            2
     'p3': (3, (16, 64, 64), (16, 20, 20), 1),                        # 196608          3
     'lidar': (2, (41, 1600, 1408), (12, 14, 16), None),              # 184729600       4
+    'box40': (2, (41, 1600, 1408), (40, 40, 40), None),              # 184729600       4
+    'box64': (2, (41, 1600, 1408), (40, 64, 64), None),              # 184729600       4
 }
 TABLE_CASES = [('p1', 0), ('p1', 1), ('p1', 37), ('p2', 1023), ('p2', 1024), ('p2', 1025),
                ('p3', 5000), ('lidar', 3000)]
@@ -71,7 +75,7 @@ def bits_equal(a, b):
     return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
-def build_rules(device, rows, batch, shape, geometry):
+def build_rules(device, rows, batch, shape, geometry, workspace=None):
     """Both phases through HipKernels with every output pre-filled with garbage."""
     from nesie_amd.kernels import HipKernels
     k = HipKernels()
@@ -83,7 +87,8 @@ def build_rules(device, rows, batch, shape, geometry):
     _, cells = k.spconv_out_shape(shape, ksize, stride, padding, subm, batch)
     sk, sr, nbr_t, counts = full(n), full(n), full(n, kvol), full(2)
     worst = None if subm else full(min(n * kvol, cells), 4)
-    k.spconv_out_sites(idx, batch, shape, ksize, stride, padding, subm, sk, sr, nbr_t, worst, counts)
+    k.spconv_out_sites(idx, batch, shape, ksize, stride, padding, subm, sk, sr, nbr_t, worst, counts,
+                       workspace)
     m, bad = counts.tolist()
     outids = idx if subm else worst[:m].clone()
     if not subm:
@@ -95,9 +100,9 @@ def build_rules(device, rows, batch, shape, geometry):
 
 # ---- tables ------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize('grid,n', TABLE_CASES)
-@pytest.mark.parametrize('geometry', list(GEOMETRIES))
-def test_tables_equal_the_brute_force_referee(hip_device, geometry, grid, n):
+def check_tables(hip_device, geometry, grid, n, rulebook):
+    """Both phases against ``rulebook`` (the brute-force referee or its vectorised form): every
+    table, the sorted keys and rows, the counts; built twice, the same bits."""
     batch, shape, _, _ = GRIDS[grid]
     rows = sites(11, grid, n)
     ksize, stride, padding, subm = GEOMETRIES[geometry]
@@ -109,7 +114,7 @@ def test_tables_equal_the_brute_force_referee(hip_device, geometry, grid, n):
         assert tuple(outids.shape) == (0, 4) and tuple(rules.nbr.shape) == (0, kvol)
         assert tuple(rules.nbr_t.shape) == (0, kvol) and pair_num.tolist() == [0] * kvol
         return
-    w_out, w_nbr, w_nbr_t, w_pairs = R.rulebook(rows, batch, shape, ksize, stride, padding, subm)
+    w_out, w_nbr, w_nbr_t, w_pairs = rulebook(rows, batch, shape, ksize, stride, padding, subm)
     got = build_rules(hip_device, rows, batch, shape, geometry)
     assert got['bad'] == 0 and got['m'] == len(w_out)
     assert same(got['outids'], w_out)
@@ -126,6 +131,56 @@ def test_tables_equal_the_brute_force_referee(hip_device, geometry, grid, n):
     again = build_rules(hip_device, rows, batch, shape, geometry)
     for name in ('outids', 'nbr', 'nbr_t', 'pair_num'):
         assert torch.equal(got[name], again[name])
+    return got
+
+
+@pytest.mark.parametrize('grid,n', TABLE_CASES)
+@pytest.mark.parametrize('geometry', list(GEOMETRIES))
+def test_tables_equal_the_brute_force_referee(hip_device, geometry, grid, n):
+    check_tables(hip_device, geometry, grid, n, R.rulebook)
+
+
+@pytest.mark.parametrize('n', [9710, 38837])
+def test_tables_where_the_scan_carries(hip_device, n):
+    """conv333s2p1 on the (41, 1600, 1408) grid: 9710 sites are 262 170 candidates, 257 tile totals
+    of the candidate flag scan; 38 837 sites are 1 048 599 candidates, 1025 sort tiles, whose
+    262 400 digit counters carry inside each of the second sort's four passes too.  The referee is
+    the vectorised rulebook, which tests/test_spconv_cpu.py proves equal to the brute force."""
+    threshold = {9710: 262144, 38837: 1048576}[n]
+    assert (n - 1) * 27 <= threshold < n * 27                       # the smallest n past it
+    got = check_tables(hip_device, 'conv333s2p1', 'box40', n, R.rulebook_fast)
+    assert got['m'] > 8000
+
+
+def test_tables_where_the_carry_reaches_valid_candidates(hip_device):
+    """With stride 2 about one candidate in eight is an output site, and the others sort last: at
+    the two sizes above every position behind the scan's carry holds an out-of-range key, whose
+    scan value nothing reads, so there the carry shows in the output count alone.  84 000 sites
+    give more than 262 144 valid candidates: output rows and nbr_t entries come from behind it."""
+    got = check_tables(hip_device, 'conv333s2p1', 'box64', 84000, R.rulebook_fast)
+    assert int(got['pair_num'].sum()) > 262144 + 10000
+
+
+@pytest.mark.parametrize('n', [1, 1025, 5000, 9710])
+@pytest.mark.parametrize('geometry', ['subm333', 'conv333s2p1'])
+def test_out_sites_stays_inside_the_workspace_it_asks_for(hip_device, geometry, n):
+    """Exactly the bytes the query returns, between two bands of 4096 bytes of 0xA5 that must stay
+    as they are; the regular conv carves that scratch twice, for n and then for n * K (9710 sites:
+    the candidate scan carries).  Every output equals the run that allocated its own workspace."""
+    from nesie_amd.kernels import HipKernels
+    guard = 4096
+    batch, shape, _, _ = GRIDS['box40']
+    rows = sites(14, 'box40', n)
+    subm = GEOMETRIES[geometry][3]
+    need = HipKernels.spconv_rules_workspace_bytes(n, 27, subm)
+    assert need > 0
+    whole = torch.full((need + 2 * guard,), 0xA5, dtype=torch.uint8, device=hip_device)
+    own = build_rules(hip_device, rows, batch, shape, geometry)
+    got = build_rules(hip_device, rows, batch, shape, geometry, whole[guard:guard + need])
+    assert bool((whole[:guard] == 0xA5).all()) and bool((whole[guard + need:] == 0xA5).all())
+    assert (got['m'], got['bad']) == (own['m'], own['bad']) and got['bad'] == 0
+    for name in ('outids', 'nbr', 'nbr_t', 'pair_num', 'sk', 'sr'):
+        assert torch.equal(got[name], own[name])
 
 
 @pytest.mark.parametrize('geometry', ['subm333', 'conv333s2p1'])

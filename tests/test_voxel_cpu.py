@@ -137,6 +137,119 @@ def test_scatter_referee_backward():
     assert g.tolist() == [[10, 20]] * 3 + [[30, 40], [0, 0]]
 
 
+# ---- the vectorised referee equals the loops, on the inputs the device tests use ------------------
+
+def identical(got, want):
+    """dtype, shape and every bit of every element"""
+    bits = (lambda a: a.view(np.uint32)) if want.dtype == np.float32 else (lambda a: a)
+    return isinstance(got, np.ndarray) and got.dtype == want.dtype and got.shape == want.shape \
+        and np.array_equal(bits(np.ascontiguousarray(got)), bits(np.ascontiguousarray(want)))
+
+
+def _voxelizer_inputs():
+    """(points, voxel_size, coors_range, max_points, max_voxels) of tests/test_voxel_gpu.py"""
+    from tests import test_voxel_gpu as G
+    for n in G.SIZES:
+        yield (G.cloud(n, n, 4, 'p2'), *G.GRIDS['p2'], 5, 200)
+    for grid, c in (('tiny', 3), ('p2', 65), ('p3', 5), ('lidar', 4)):
+        yield (G.cloud(17, 3000, c, grid), *G.GRIDS[grid], 5, 8 if grid == 'tiny' else 2500)
+    for max_points in (1, 5):
+        yield (G.cloud(3, 1500, 4, 'p2', 'one_cell'), *G.GRIDS['p2'], max_points, 40)
+    yield (G.cloud(4, 1300, 4, 'p3', 'outside'), *G.GRIDS['p3'], 5, 40)
+    a, b, c = [0.1, 0.1, 0.1], [0.5, 0.1, 0.1], [0.1, 0.5, 0.1]
+    xyz = np.float32([a, b, a, c, b, c, a, [9.0, 0.1, 0.1], b, a])
+    midstream = np.concatenate([xyz, np.arange(10, dtype=np.float32)[:, None]], axis=1)
+    for max_voxels in (2, 3):
+        yield (midstream, *G.GRIDS['p2'], 3, max_voxels)
+    for max_voxels in (150, 400):
+        yield (G.cloud(61, 5000, 4, 'p3'), *G.GRIDS['p3'], 4, max_voxels)
+    for cells, cr in G.BOUNDARY_GRIDS.items():
+        yield (G.cloud(int(cells) % 1000, 3129, 4, ([1.0, 1.0, 1.0], cr)), [1.0, 1.0, 1.0], cr, 5,
+               2500)
+    vs, cr = G.GRIDS['lidar']
+    for order in ('descending', 'top_byte', 'alternating'):
+        coors = G.keys_to_coors(G.ordered_keys(order))
+        points = np.zeros((len(coors), 4), dtype=np.float32)
+        points[:, :3] = (np.float64(cr[:3]) + (coors[:, ::-1] + 0.5) * np.float64(vs))
+        points[:, 3] = np.arange(len(coors))
+        yield (points, vs, cr, 5, 3000 if order == 'descending' else 40)
+    # a small slice of the carrying sizes' own cloud and cap
+    yield (G.cloud(262145, 262145, 4, 'lidar')[:9000], vs, cr, 5, 1000)
+
+
+def test_fast_hard_voxelizer_equals_the_walk_bit_for_bit(golden):
+    cases = 0
+    for points, vs, cr, max_points, max_voxels in _voxelizer_inputs():
+        want = R.hard_voxelize(points, vs, cr, max_points, max_voxels)
+        got = R.hard_voxelize_fast(points, vs, cr, max_points, max_voxels)
+        for g, w in zip(got, want):
+            assert identical(g, w), (len(points), vs, max_points, max_voxels)
+        cases += 1
+    assert cases == 29
+    for name in golden['names'].tolist():
+        g = {k.split('/', 1)[1]: v for k, v in golden.items() if k.startswith(name + '/')}
+        got = R.hard_voxelize_fast(g['points'], g['voxel_size'].tolist(), g['coors_range'].tolist(),
+                                   int(g['max_points']), int(g['max_voxels']))
+        for a, key in zip(got, ('voxels', 'coors', 'num_points_per_voxel')):
+            assert identical(a, g[key]), name
+
+
+def _scatter_inputs():
+    """(feats, coors, dims) of tests/test_voxel_gpu.py; dims None: the functional's own bounds"""
+    from tests import test_voxel_gpu as G
+    for n in G.SIZES:
+        yield (*G.scatter_case(n, n, 4, (6, 7, 5)), (6, 7, 5))
+    for dims, c in (((1, 2, 2), 3), ((4, 40, 40), 65), ((16, 128, 128), 5), ((40, 1600, 1408), 4),
+                    ((3, 3, 3), 260)):
+        yield (*G.scatter_case(23, 700 if c == 260 else 3129, c, dims), dims)
+    yield (*G.scatter_case(31, 2000, 4, (6, 7, 5), invalid=0), (6, 7, 5))
+    feats, _ = G.scatter_case(32, 1500, 4, (6, 7, 5))
+    coors = np.full((1500, 3), -1, dtype=np.int32)
+    coors[::3] = [0, 7, 0]
+    yield feats, coors, (6, 7, 5)
+    yield (*G.scatter_case(33, 3129, 5, (6, 7, 5), ties=True, nans=True), (6, 7, 5))
+    yield (*G.scatter_case(34, 3129, 5, (6, 7, 5), ties=True), (6, 7, 5))
+    rng = np.random.default_rng(35)
+    coors = np.zeros((1400, 3), dtype=np.int32)
+    coors[:, 2] = rng.integers(0, 3, 1400)
+    coors[rng.random(1400) < 0.1] = -1
+    yield rng.standard_normal((1400, 6)).astype(np.float32), coors, (1, 1, 3)
+    feats, coors = G.scatter_case(41, 3129, 7, (6, 7, 5), ties=True)
+    coors[coors[:, 2] == 5, 2] = -1
+    yield feats, coors, None
+    for dims in G.BOUNDARY_DIMS:
+        yield (*G.scatter_case(sum(dims) % 1000, 3129, 4, dims, invalid=0.075), dims)
+    for order in ('descending', 'top_byte', 'alternating'):
+        feats, _ = G.scatter_case(36, 5000, 4, G.ORDER_DIMS, ties=order != 'descending')
+        yield feats, G.keys_to_coors(G.ordered_keys(order)), G.ORDER_DIMS
+    # a small slice of the carrying sizes' own generator, both feature ranges
+    for span in (1, 4):
+        feats, coors = G.box_scatter_case(145, 262145, 4, (40, 1600, 1408), span=span)
+        coors = coors[:9000].copy()
+        valid = ((coors >= 0) & (coors < np.int32([40, 1600, 1408]))).all(axis=1)
+        coors[valid, 2] %= 8                                   # several points to a voxel
+        yield feats[:9000], coors, (40, 1600, 1408)
+
+
+def test_fast_scatter_equals_the_loops_bit_for_bit():
+    cases = 0
+    for feats, coors, dims in _scatter_inputs():
+        n, c = feats.shape
+        grad_voxel = np.random.default_rng(n + c).standard_normal((max(n, 1), c)).astype(np.float32)
+        for reduce_type in ('sum', 'mean', 'max'):
+            want = R.scatter_forward(feats, coors, reduce_type, dims)
+            got = R.scatter_forward_fast(feats, coors, reduce_type, dims)
+            for g, w in zip(got, want):
+                assert identical(g, w), (n, c, dims, reduce_type)
+            w_out, w_vc, w_map, w_cnt = want
+            gv = grad_voxel[:len(w_vc)]
+            w_grad = R.scatter_backward(gv, feats, w_out, w_map, w_cnt, reduce_type)
+            g_grad = R.scatter_backward_fast(gv, feats, w_out, w_map, w_cnt, reduce_type)
+            assert identical(g_grad, w_grad), (n, c, dims, reduce_type)
+        cases += 1
+    assert cases == 31
+
+
 def test_the_four_names_are_real():
     from nesie_amd import mmdet3d_ops
     from nesie_amd.mmdet3d_ops import voxel as mod

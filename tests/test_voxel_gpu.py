@@ -3,11 +3,27 @@
 float, every gradient -- and the goldens of the reference's CPU voxelizers; the modules through
 autograd; run-to-run equality; graph capture; refusals before allocation.
 
-Sizes: the sort works on tiles of 1024 keys (VX_SORT_TILE) and the scan on tiles of 1024 ints
-(VX_SCAN_TILE; it scans N flags and 256 x ceil(N / 1024) digit counters), so N goes one below, at
+Sizes: the sort works on tiles of 1024 keys (IX_SORT_TILE) and the scan on tiles of 1024 ints
+(IX_SCAN_TILE; it scans N flags and 256 x ceil(N / 1024) digit counters), so N goes one below, at
 and one above 1024, 3129 spans four tiles of the flag scan, 5000 puts the counter scan one tile
 past its first (1280 counters) and 9000 gives it three (2304).  The grids need 1, 2, 3 and 4
-eight-bit passes."""
+eight-bit passes.
+
+The scan's second level walks the tile totals 256 at a time with a carry: 262 144 flags are 256
+totals (one trip, no carry), 262 145 are 257 (the carry's first use, for one element), 393 217 are
+385 (a third of the elements behind the carry) and 1 048 577 points are 1025
+flag tiles and 1025 sort tiles, whose 262 400 digit counters are 257 totals, so there the carry
+runs inside every sort pass too.  At those sizes the referee is the vectorised form of
+tests/_voxel_ref.py (tests/test_voxel_cpu.py proves it equal to the loops, bit for bit, on every
+small input of this file) and the reduced features are small integers, whose fp32 sums are exact
+in any order; the summation order itself is pinned by the small sizes on arbitrary floats.
+
+Pass counts: the out-of-range key is `cells` itself, so at 2^8, 2^16 and 2^24 cells it is the only
+key with a bit in the top pass; the grids and dims of the boundary tests sit one below and exactly
+at those counts, and at 2^31 - 1, the largest accepted.  The key-order tests feed the sort what a
+random draw never does: strictly descending keys, keys that differ only in the top byte, two
+alternating cells.  The guard-band tests hand each op exactly the workspace bytes its query
+returns, between two bands that must stay untouched."""
 import os
 
 import numpy as np
@@ -47,7 +63,7 @@ def dev(a, device):
 def cloud(seed, n, c, grid, mode='mixed'):
     """(n, c) float32: half the points crowd a few cells (so cells overflow max_points), the rest
     are uniform over the range grown by a margin (so out-of-range points are interleaved)."""
-    vs, cr = GRIDS[grid]
+    vs, cr = GRIDS[grid] if isinstance(grid, str) else grid
     rng = np.random.default_rng(seed)
     lo, hi = np.float64(cr[:3]), np.float64(cr[3:])
     pts = rng.standard_normal((n, c)).astype(np.float32)
@@ -79,12 +95,14 @@ def run_hard(device, points, vs, cr, max_points, max_voxels, workspace=None):
     return voxels, coors, num, voxel_num
 
 
-def check_voxelizers(device, points, vs, cr, max_points, max_voxels, want=None):
+def check_voxelizers(device, points, vs, cr, max_points, max_voxels, want=None, fast=False):
+    """``fast``: the vectorised referee, for sizes the serial walk cannot reach."""
     from nesie_amd.kernels import HipKernels
     from nesie_amd.mmdet3d_ops import voxelization
     if want is None:
+        hard = R.hard_voxelize_fast if fast else R.hard_voxelize
         want = (R.dynamic_voxelize(points, vs, cr),
-                *R.hard_voxelize(points, vs, cr, max_points, max_voxels))
+                *hard(points, vs, cr, max_points, max_voxels))
     w_dyn, w_vox, w_coors, w_num = want
     n = len(points)
     dyn = torch.full((n, 3), GARBAGE_I, dtype=torch.int32, device=device)
@@ -168,6 +186,112 @@ def test_goldens_of_the_reference_cpu_programs(hip_device):
                          (g['dynamic_coors'], g['voxels'], g['coors'], g['num_points_per_voxel']))
 
 
+# 256, 257, 385 and 1025 tile totals of the flag scan.  At 262 145 a single element lies past the
+# first 256 totals, and the cap (or an invalid key sorted last) can hide what the carry gives it;
+# 393 217 puts a third of the elements there while the sort's counters still scan in one trip.
+CARRY_SIZES = (262144, 262145, 393217, 1048577)
+
+
+def occupied_cells(points, vs, cr):
+    dyn = R.dynamic_voxelize(points, vs, cr)
+    gx, gy, _ = R.grid_size(vs, cr)
+    inside = dyn[dyn[:, 0] != -1].astype(np.int64)
+    return len(np.unique((inside[:, 0] * gy + inside[:, 1]) * gx + inside[:, 2]))
+
+
+@pytest.mark.parametrize('n', CARRY_SIZES)
+def test_voxelizers_where_the_scan_carries(hip_device, n):
+    """Four passes; half the points in 12 hot cells, out-of-range points interleaved; the cap on
+    the voxel count (`*capped` of the scan) is reached mid-stream."""
+    vs, cr = GRIDS['lidar']
+    points = cloud(n, n, 4, 'lidar')
+    max_voxels = 20000
+    assert occupied_cells(points, vs, cr) > max_voxels
+    dyn, _, w_coors, w_num = check_voxelizers(hip_device, points, vs, cr, 5, max_voxels, fast=True)
+    assert len(w_coors) == max_voxels and (w_num == 5).any() and (w_num < 5).any()
+    assert (dyn == -1).any()
+
+
+def test_one_cell_across_257_tiles_keeps_the_lowest_indices_in_order(hip_device):
+    """Every point in one cell: the voxel holds points 0 .. 4 in index order only if every pass
+    kept the input order across all 257 tiles."""
+    vs, cr = GRIDS['lidar']
+    points = cloud(5, 262145, 4, 'lidar', 'one_cell')
+    _, w_vox, w_coors, w_num = check_voxelizers(hip_device, points, vs, cr, 5, 40, fast=True)
+    assert w_coors.tolist() == [[0, 0, 1]] and w_num.tolist() == [5]
+    assert np.array_equal(w_vox[0], points[:5])
+
+
+# name: (coors_range of a grid of voxel size 1.0)                       cells        passes
+BOUNDARY_GRIDS = {
+    '255': [0.0, 0.0, 0.0, 15.0, 17.0, 1.0],                          # 2^8 - 1      1
+    '256': [0.0, 0.0, 0.0, 16.0, 16.0, 1.0],                          # 2^8          2
+    '65535': [0.0, 0.0, 0.0, 255.0, 257.0, 1.0],                      # 2^16 - 1     2
+    '65536': [0.0, 0.0, 0.0, 256.0, 256.0, 1.0],                      # 2^16         3
+    '16777215': [0.0, 0.0, 0.0, 4095.0, 4097.0, 1.0],                 # 2^24 - 1     3
+    '16777216': [0.0, 0.0, 0.0, 256.0, 256.0, 256.0],                 # 2^24         4
+}
+
+
+@pytest.mark.parametrize('cells', list(BOUNDARY_GRIDS))
+def test_voxelizers_at_every_pass_boundary(hip_device, cells):
+    """Grids of one cell below and exactly 2^8, 2^16, 2^24 cells: at the power of two the
+    out-of-range key is the only one the top pass moves.  Points in the first and the last cell,
+    some outside."""
+    vs, cr = [1.0, 1.0, 1.0], BOUNDARY_GRIDS[cells]
+    gx, gy, gz = R.grid_size(vs, cr)
+    assert gx * gy * gz == int(cells)
+    points = cloud(int(cells) % 1000, 3129, 4, (vs, cr))
+    points[[0, 7, 1500], :3] = [0.5, 0.5, 0.5]
+    points[[1, 9, 3128], :3] = [gx - 0.5, gy - 0.5, gz - 0.5]
+    dyn, _, w_coors, _ = check_voxelizers(hip_device, points, vs, cr, 5, 2500)
+    assert dyn[0].tolist() == [0, 0, 0] and dyn[1].tolist() == [gz - 1, gy - 1, gx - 1]
+    assert w_coors[0].tolist() == [0, 0, 0] and w_coors[1].tolist() == [gz - 1, gy - 1, gx - 1]
+    assert (dyn == -1).any() and 12 < len(w_coors) < 2500
+
+
+# ---- key orders a random draw never produces -------------------------------------------------
+
+ORDER_DIMS = (40, 1600, 1408)               # the lidar grid as (z, y, x): 90 112 000 cells, 4 passes
+
+
+def ordered_keys(order, n=5000):
+    cells = int(np.prod(ORDER_DIMS))
+    if order == 'descending':               # strictly: every key its own cell
+        keys = cells - 1 - np.arange(n, dtype=np.int64) * (cells // n)
+    elif order == 'top_byte':               # the three low passes see one digit each
+        keys = (np.random.default_rng(6).integers(0, (cells >> 24) + 1, n) << 24) + 1234567
+    else:                                   # 'alternating': the first and the last cell
+        keys = np.where(np.arange(n) % 2 == 0, 0, cells - 1).astype(np.int64)
+    assert keys.min() >= 0 and keys.max() < cells
+    return keys
+
+
+def keys_to_coors(keys):
+    _, dy, dx = ORDER_DIMS
+    return np.stack([keys // (dy * dx), keys // dx % dy, keys % dx], axis=1).astype(np.int32)
+
+
+@pytest.mark.parametrize('order', ['descending', 'top_byte', 'alternating'])
+def test_voxelizers_on_ordered_keys(hip_device, order):
+    vs, cr = GRIDS['lidar']
+    coors = keys_to_coors(ordered_keys(order))
+    points = np.random.default_rng(7).standard_normal((len(coors), 4)).astype(np.float32)
+    centre = np.float64(cr[:3]) + (coors[:, ::-1] + 0.5) * np.float64(vs)
+    points[:, :3] = centre.astype(np.float32)
+    max_voxels = 3000 if order == 'descending' else 40
+    dyn, w_vox, w_coors, w_num = check_voxelizers(hip_device, points, vs, cr, 5, max_voxels)
+    assert np.array_equal(dyn, coors)                       # the points sit in the cells meant
+    if order == 'descending':     # first appearance = input order: the first 3000 points, one each
+        assert np.array_equal(w_coors, coors[:3000]) and (w_num == 1).all()
+        assert np.array_equal(w_vox[:, 0], points[:3000])
+    elif order == 'top_byte':
+        assert len(w_coors) == 6 and (w_num == 5).all()
+    else:
+        assert w_coors.tolist() == [[0, 0, 0], [39, 1599, 1407]]
+        assert np.array_equal(w_vox[0], points[0:10:2]) and np.array_equal(w_vox[1], points[1:10:2])
+
+
 # ---- dynamic_scatter -----------------------------------------------------------------------
 
 def scatter_case(seed, n, c, dims, invalid=0.15, ties=False, nans=False):
@@ -214,17 +338,19 @@ def run_scatter(device, feats, coors, dims, reduce_type, workspace=None, grad_vo
     return out
 
 
-def check_scatter(device, feats, coors, dims, reduce_type):
+def check_scatter(device, feats, coors, dims, reduce_type, fast=False):
+    """``fast``: the vectorised referee, for sizes the loops cannot reach."""
+    forward = R.scatter_forward_fast if fast else R.scatter_forward
+    backward = R.scatter_backward_fast if fast else R.scatter_backward
     n, c = feats.shape
-    w_out, w_vc, w_map, w_cnt = R.scatter_forward(feats, coors, reduce_type, dims)
+    w_out, w_vc, w_map, w_cnt = forward(feats, coors, reduce_type, dims)
     grad_voxel = np.random.default_rng(n + c).standard_normal((max(n, 1), c)).astype(np.float32)
     got = run_scatter(device, feats, coors, dims, reduce_type, grad_voxel=grad_voxel)
     assert got['m'] == len(w_vc)
     assert same(got['voxel_coors'], w_vc) and same(got['coors_map'], w_map)
     assert same(got['reduce_count'], w_cnt) and same(got['voxel_feats'], w_out)
     if 'grad_feats' in got:
-        w_grad = R.scatter_backward(grad_voxel[:len(w_vc)], feats, w_out, w_map, w_cnt,
-                                    reduce_type)
+        w_grad = backward(grad_voxel[:len(w_vc)], feats, w_out, w_map, w_cnt, reduce_type)
         assert same(got['grad_feats'], w_grad)
     return w_out, w_vc, w_map, w_cnt
 
@@ -285,6 +411,130 @@ def test_scatter_voxels_of_several_hundred_points(hip_device, reduce_type):
     feats = rng.standard_normal((n, 6)).astype(np.float32)
     _, _, _, w_cnt = check_scatter(hip_device, feats, coors, (1, 1, 3), reduce_type)
     assert w_cnt.min() > 300
+
+
+SCATTER_BOX = (4, 64, 64)
+
+
+def box_scatter_case(seed, n, c, dims, span=4, box=SCATTER_BOX, invalid=0.1):
+    """Coordinates from two sub-boxes of ``dims``, one in each extreme corner (so voxels hold
+    several points and the keys span every byte); about ``invalid`` of the rows are invalid, a
+    negative entry or one at its bound.  Features are integers in [-span, span]: every fp32 sum
+    is exact whatever its order (below 2^24), and with span 1 most voxels hold their maximum more
+    than once."""
+    rng = np.random.default_rng(seed)
+    coors = np.stack([rng.integers(0, b, n) for b in box], axis=1).astype(np.int32)
+    far = rng.random(n) < 0.5
+    coors[far] += np.int32(dims) - np.int32(box)
+    bad = np.flatnonzero(rng.random(n) < invalid)
+    col = rng.integers(0, 3, len(bad))
+    coors[bad, col] = np.where(rng.random(len(bad)) < 0.7, -1, np.int32(dims)[col])
+    feats = rng.integers(-span, span + 1, (n, c)).astype(np.float32)
+    return feats, coors
+
+
+@pytest.mark.parametrize('n,reduce_type', [(262145, 'sum'), (262145, 'mean'), (262145, 'max'),
+                                           (393217, 'max'), (1048577, 'mean'), (1048577, 'max')])
+def test_scatter_where_the_scan_carries(hip_device, n, reduce_type):
+    """257 tile totals of the flag scan at 262 145 rows; at 1 048 577 the digit counters of every
+    one of the four sort passes carry too.  max: ties in most voxels, the gradient to the lowest
+    index -- where a sort that lost its stability in a later tile would show."""
+    dims = (40, 1600, 1408)
+    feats, coors = box_scatter_case(n % 1000, n, 4, dims, span=1 if reduce_type == 'max' else 4)
+    w_out, w_vc, w_map, w_cnt = check_scatter(hip_device, feats, coors, dims, reduce_type, fast=True)
+    assert 0.05 < (w_map == -1).mean() < 0.15 and w_cnt.min() >= 1 and np.median(w_cnt) >= 3
+    assert w_vc[0, 0] < SCATTER_BOX[0] and w_vc[-1, 0] >= dims[0] - SCATTER_BOX[0]
+    if reduce_type == 'max':
+        valid = w_map >= 0
+        top = (feats[valid] == w_out[w_map[valid]])[:, 0]
+        tied = np.bincount(w_map[valid][top], minlength=len(w_cnt)) > 1
+        assert tied.mean() > 0.5                            # most voxels hold their maximum twice
+
+
+BOUNDARY_DIMS = [(1, 15, 17), (1, 16, 16), (1, 255, 257), (1, 256, 256), (1, 4095, 4097),
+                 (256, 256, 256), (1, 1, 2147483647)]
+
+
+@pytest.mark.parametrize('dims', BOUNDARY_DIMS)
+def test_scatter_at_every_pass_boundary(hip_device, dims):
+    """dims whose product is one below and exactly 2^8, 2^16, 2^24, and 2^31 - 1, the largest
+    accepted: rows at cell 0 and at the last valid cell, about a tenth invalid."""
+    assert int(np.prod(np.int64(dims))) in (255, 256, 65535, 65536, 16777215, 16777216, 2 ** 31 - 1)
+    feats, coors = scatter_case(sum(dims) % 1000, 3129, 4, dims, invalid=0.075)
+    coors[[0, 5, 2000]] = [0, 0, 0]
+    coors[[1, 7, 3128]] = [d - 1 for d in dims]
+    for reduce_type in ('sum', 'mean', 'max'):
+        _, w_vc, w_map, _ = check_scatter(hip_device, feats, coors, dims, reduce_type)
+        assert w_vc[0].tolist() == [0, 0, 0] and w_vc[-1].tolist() == [d - 1 for d in dims]
+        assert 0.05 < (w_map == -1).mean() < 0.15
+
+
+@pytest.mark.parametrize('reduce_type', ['sum', 'mean', 'max'])
+@pytest.mark.parametrize('order', ['descending', 'top_byte', 'alternating'])
+def test_scatter_on_ordered_keys(hip_device, order, reduce_type):
+    coors = keys_to_coors(ordered_keys(order))
+    feats, _ = scatter_case(36, len(coors), 4, ORDER_DIMS, ties=order != 'descending')
+    _, w_vc, w_map, w_cnt = check_scatter(hip_device, feats, coors, ORDER_DIMS, reduce_type)
+    if order == 'descending':     # voxel rows ascend: the map is the input order reversed
+        assert np.array_equal(w_map, np.arange(len(coors) - 1, -1, -1)) and (w_cnt == 1).all()
+    elif order == 'top_byte':
+        assert len(w_vc) == 6
+    else:
+        assert w_map[:4].tolist() == [0, 1, 0, 1] and w_cnt.tolist() == [2500, 2500]
+
+
+# ---- workspace guard bands -----------------------------------------------------------------
+
+GUARD = 4096
+
+
+class Guarded:
+    """``need`` bytes of workspace between two bands of GUARD bytes, everything filled with 0xA5."""
+
+    def __init__(self, need, device):
+        self.need = need
+        self.whole = torch.full((need + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=device)
+        self.workspace = self.whole[GUARD:GUARD + need]
+
+    def bands_untouched(self):
+        return bool((self.whole[:GUARD] == 0xA5).all()) and \
+            bool((self.whole[GUARD + self.need:] == 0xA5).all())
+
+
+def bits_equal(a, b):
+    if a.dtype == torch.float32:
+        a, b = a.view(torch.int32), b.view(torch.int32)
+    return a.shape == b.shape and torch.equal(a, b)
+
+
+@pytest.mark.parametrize('n', [1, 1025, 5000, 262145])
+def test_hard_voxelize_stays_inside_the_workspace_it_asks_for(hip_device, n):
+    from nesie_amd.kernels import HipKernels
+    vs, cr = GRIDS['lidar']
+    points = cloud(80 + n % 100, n, 4, 'lidar')
+    _, cells = HipKernels.voxel_grid_size(vs, cr)
+    guarded = Guarded(HipKernels.voxel_workspace_bytes(n, cells), hip_device)
+    assert guarded.need > 0
+    own = run_hard(hip_device, points, vs, cr, 5, 300)
+    got = run_hard(hip_device, points, vs, cr, 5, 300, guarded.workspace)
+    assert guarded.bands_untouched()
+    for a, b in zip(got, own):
+        assert bits_equal(a, b)
+
+
+@pytest.mark.parametrize('n', [1, 1025, 5000, 262145])
+def test_scatter_forward_stays_inside_the_workspace_it_asks_for(hip_device, n):
+    from nesie_amd.kernels import HipKernels
+    dims = (40, 1600, 1408)
+    feats, coors = box_scatter_case(90 + n % 100, n, 4, dims)
+    guarded = Guarded(HipKernels.voxel_workspace_bytes(n, int(np.prod(dims))), hip_device)
+    assert guarded.need > 0
+    own = run_scatter(hip_device, feats, coors, dims, 'mean')
+    got = run_scatter(hip_device, feats, coors, dims, 'mean', guarded.workspace)
+    assert guarded.bands_untouched()
+    assert got['m'] == own['m'] and set(got) == set(own)
+    for name in ('voxel_feats', 'voxel_coors', 'coors_map', 'reduce_count'):
+        assert bits_equal(got[name], own[name])
 
 
 # ---- the modules through autograd ----------------------------------------------------------
