@@ -89,20 +89,8 @@ __global__ __launch_bounds__(MF_COLS) void aa_matrix_forward_kernel(AaPair A, in
 }
 
 // ---- matrix backward ---------------------------------------------------------------------------
-// Sum over the 64 lanes of a wave in a fixed tree (lane ^ 1, lane ^ 2, mirror in 8, mirror in 16 by
-// DPP, then the halves of 32 and of 64); every lane ends with the same bits.
-__device__ __forceinline__ float wave_sum_fixed(float v) {
-  v += __uint_as_float(dppm<0xB1>(__float_as_uint(v)));
-  v += __uint_as_float(dppm<0x4E>(__float_as_uint(v)));
-  v += __uint_as_float(dppm<0x141>(__float_as_uint(v)));
-  v += __uint_as_float(dppm<0x140>(__float_as_uint(v)));
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 // grad1[b, i, :] = sum_j grad_out[b, i, j] * d out[b, i, j] / d box1[b, i]: one wave per row, lane l
-// takes the columns l, l + 64, ... in ascending order, then the tree.
+// takes the columns l, l + 64, ... in ascending order, then the fixed tree of wave_sum_dpp.
 constexpr int BR_WAVES = 4;
 
 __global__ __launch_bounds__(64 * BR_WAVES) void aa_matrix_backward_rows_kernel(
@@ -124,7 +112,7 @@ __global__ __launch_bounds__(64 * BR_WAVES) void aa_matrix_backward_rows_kernel(
     for (int c = 0; c < 6; ++c) acc[c] += gj * j1[c];
   }
 #pragma unroll
-  for (int c = 0; c < 6; ++c) acc[c] = wave_sum_fixed(acc[c]);
+  for (int c = 0; c < 6; ++c) acc[c] = wave_sum_dpp<64>(acc[c]);
   if (lane == 0) store6(grad1 + row * 6, acc);
 }
 

@@ -4,12 +4,13 @@
 // which gives every centre one thread that scans all N points serially.  Here a
 // WAVE owns CPW centres: its 64 lanes test 64 consecutive points at a time
 // (one dense 768-byte load shared by the CPW centres), a ballot gives the hit
-// mask, and mbcnt gives each hit lane its rank, so hits land in ascending point
+// mask, and wave_rank gives each hit lane its rank, so hits land in ascending point
 // index exactly as the serial scan would record them.  The row is assembled in
 // LDS and written out once: slot s = s-th hit for s < cnt, the first hit for
 // s >= cnt ("first hit back-fills all slots", .cu:44-48), untouched if cnt == 0.
 #include "common.h"
 #include "fps_keys.h"
+#include "wave_sort.h"
 
 namespace nesie {
 
@@ -59,9 +60,7 @@ __global__ __launch_bounds__(BQ_BLOCK) void ball_query_kernel(
           float d2 = sqdist_form<FORM>(cx[c] - x, cy[c] - y, cz[c] - z);
           bool hit = valid && (d2 == 0.f || (d2 >= min_r2 && d2 < max_r2));
           unsigned long long mask = __ballot(hit);
-          int rank = __builtin_amdgcn_mbcnt_hi(
-              (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-          int pos = cnt[c] + rank;
+          int pos = cnt[c] + wave_rank(mask);
           if (hit && pos < nsample) slots[c * nsample + pos] = k;
           cnt[c] += __popcll(mask);
           if (cnt[c] < nsample) all_full = false;
@@ -95,33 +94,9 @@ __global__ __launch_bounds__(BQ_BLOCK) void ball_query_kernel(
 // The reference records hits in ascending point index and stops at nsample (.cu:38-52), i.e.
 // it returns the nsample SMALLEST hit indices in ascending order: here one wave per centre
 // collects the hits of the ~10 surviving buckets (of 625 at 40 000 points), sorts 64 at a time
-// with a bitonic network in registers and keeps the 64 smallest, then writes the row as the
-// brute-force kernel does.  nsample <= 64.
-__device__ __forceinline__ unsigned bq_sort64(unsigned v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const unsigned o = (unsigned)__shfl_xor((int)v, j, 64);
-      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-      v = (up == lower) ? (v < o ? v : o) : (v > o ? v : o);
-    }
-  }
-  return v;
-}
-
-// best, add: ascending over the lanes; returns the 64 smallest of the 128, ascending
-__device__ __forceinline__ unsigned bq_merge_low64(unsigned best, unsigned add, int lane) {
-  const unsigned rev = (unsigned)__shfl((int)add, 63 - lane, 64);
-  unsigned v = best < rev ? best : rev;  // bitonic, holds the 64 smallest
-#pragma unroll
-  for (int j = 32; j >= 1; j >>= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)v, j, 64);
-    v = ((lane & j) == 0) ? (v < o ? v : o) : (v > o ? v : o);
-  }
-  return v;
-}
-
+// with a bitonic network in registers (wave_sort64) and keeps the 64 smallest (wave_merge64), then
+// writes the row as the brute-force kernel does.  nsample <= 64.  The hits wait for their sort in a
+// pending list private to the wave, which needs no barrier: wave_pend_push (wave_sort.h) says why.
 constexpr int BQI_WAVES = 4;
 
 __global__ __launch_bounds__(BQI_WAVES * 64) void ball_query_indexed_kernel(
@@ -144,6 +119,10 @@ __global__ __launch_bounds__(BQI_WAVES * 64) void ball_query_indexed_kernel(
 
   unsigned best = 0xFFFFFFFFu;  // lane i: i-th smallest hit index so far
   int npend = 0, total = 0;
+  auto merge = [&](unsigned v) {
+    v = wave_sort64(v, lane);
+    wave_merge64<false>(best, v, lane);
+  };
   for (int s0 = 0; s0 < nb; s0 += 64) {
     const int bid = s0 + lane;
     bool act = false;
@@ -162,27 +141,10 @@ __global__ __launch_bounds__(BQI_WAVES * 64) void ball_query_indexed_kernel(
       const float4 p = pts[valid ? s : n - 1];
       const float d2 = sqdist_nofma(cx - p.x, cy - p.y, cz - p.z);
       const bool hit = valid && (d2 == 0.f || (d2 >= min_r2 && d2 < max_r2));
-      const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
-      if (hm) {
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32),
-                                                   __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0));
-        if (hit) pend[npend + rank] = (unsigned)k_of_key_lo(__float_as_uint(p.w), L);
-        const int got = __popcll(hm);
-        npend += got; total += got;
-        if (npend >= 64) {  // npend < 128 always: at most 63 carried + 64 new
-          const unsigned v = bq_sort64(pend[lane], lane);
-          best = bq_merge_low64(best, v, lane);
-          const unsigned carry = pend[64 + lane];
-          npend -= 64;
-          if (lane < npend) pend[lane] = carry;
-        }
-      }
+      total += wave_pend_push(pend, npend, lane, hit, (unsigned)k_of_key_lo(__float_as_uint(p.w), L), merge);
     }
   }
-  if (npend > 0) {
-    const unsigned v = bq_sort64(lane < npend ? pend[lane] : 0xFFFFFFFFu, lane);
-    best = bq_merge_low64(best, v, lane);
-  }
+  wave_pend_flush(pend, npend, lane, 0xFFFFFFFFu, merge);
   if (total > 0) {  // no hit: the row stays as the caller zeroed it (.cu:38-52)
     const int have = total < nsample ? total : nsample;
     const unsigned first = (unsigned)__builtin_amdgcn_readfirstlane((int)best);
@@ -212,13 +174,11 @@ extern "C" int nesie_ball_query_wrapper(int b, int n, int m, float min_radius,
   const int per_block = (BQ_BLOCK / 64) * BQ_CPW;
   const long long groups = cdiv(m, per_block);
   NESIE_REQUIRE(groups * b < (1ll << 31), W);
-#define BQ(FORM)                                                                                \
-  hipLaunchKernelGGL(ball_query_kernel<FORM>, dim3((unsigned)(groups * b)), dim3(BQ_BLOCK), lds, \
-                     (hipStream_t)stream, b, n, m, min_radius, max_radius, nsample, new_xyz, xyz, idx)
-  if (distance_form() == 1) BQ(1);
-  else if (distance_form() == 2) BQ(2);
-  else BQ(0);
-#undef BQ
+  with_distance_form([&](auto form) {
+    hipLaunchKernelGGL(ball_query_kernel<decltype(form)::value>, dim3((unsigned)(groups * b)),
+                       dim3(BQ_BLOCK), lds, (hipStream_t)stream, b, n, m, min_radius, max_radius, nsample,
+                       new_xyz, xyz, idx);
+  });
   return check_launch(W);
 }
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/nesie_ops.h"
 
 namespace nesie {
@@ -69,6 +71,17 @@ __device__ __forceinline__ float sqdist_form(float dx, float dy, float dz) {
   return sqdist_nofma(dx, dy, dz);
 }
 
+// Calls f(std::integral_constant<int, FORM>()) with FORM = distance_form(): a launcher writes its
+// kernel<decltype(form)::value> once, inside a generic lambda.
+template <typename F>
+inline void with_distance_form(F &&f) {
+  switch (distance_form()) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    default: f(std::integral_constant<int, 0>()); break;
+  }
+}
+
 // 64-bit max across the 64 lanes of a wave (result valid in every lane).
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll
@@ -88,6 +101,29 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// v of the lane that DPP control CTRL names (full row and bank masks): inside a row of 16 lanes, no
+// LDS, full rate
+template <int CTRL>
+__device__ __forceinline__ unsigned dppm(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false);
+}
+
+// Sum across each run of LANES (32 or 64) consecutive lanes, result in every lane of the run, in
+// another fixed order: lane ^ 1, lane ^ 2, the mirror within 8 and the mirror within 16 by DPP,
+// then xor 16 (and xor 32).  Four LDS-free steps, but not wave_sum's order, so a float sum differs
+// from wave_sum's bitwise: the outputs pinned on one must not move to the other.
+template <int LANES>
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+  static_assert(LANES == 32 || LANES == 64, "a half or a whole wave");
+  v += __uint_as_float(dppm<0xB1>(__float_as_uint(v)));   // quad_perm [1,0,3,2]
+  v += __uint_as_float(dppm<0x4E>(__float_as_uint(v)));   // quad_perm [2,3,0,1]
+  v += __uint_as_float(dppm<0x141>(__float_as_uint(v)));  // row_half_mirror
+  v += __uint_as_float(dppm<0x140>(__float_as_uint(v)));  // row_mirror
+  v += __shfl_xor(v, 16, 64);
+  if (LANES == 64) v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
 // Sum over a workgroup of BLOCK threads, result in every thread: wave_sum, then the waves' sums
 // in ascending wave order.  sh: BLOCK / 64 floats of LDS; the barrier in front lets a caller hand
 // in the same sh for one sum after another.
@@ -104,12 +140,7 @@ __device__ __forceinline__ float block_sum(float v, float *sh) {
   return t;
 }
 
-// ---- DPP helpers for reductions inside a row of <= 16 lanes (no LDS, full rate)
-template <int CTRL>
-__device__ __forceinline__ unsigned dppm(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false);
-}
-
+// ---- arg-max inside a row of <= 16 lanes, through dppm
 // (value, index) max with smallest-index tie-break, exchanged with the lane given by CTRL
 template <int CTRL>
 __device__ __forceinline__ void argmax_step(float &v, int &i) {

@@ -13,6 +13,7 @@
 // are used here.  Ties keep the earlier index in the better slot (strict <).
 #include "common.h"
 #include "index_sort.h"
+#include "wave_sort.h"
 #include <math.h>
 
 namespace nesie {
@@ -20,18 +21,21 @@ namespace nesie {
 constexpr int NN_BLOCK = 256;
 constexpr int NN_TILE = 1024;  // known points per LDS tile (12 KB)
 
+// The three nearest of the m points of `known` to (ux, uy, uz): squared distances b1 <= b2 <= b3
+// and their indices (+inf and 0 where m < 3).
+struct ThreeNN {
+  float b1, b2, b3;
+  int i1, i2, i3;
+};
+
+// `known` streams through the workgroup's tile `kk` with two barriers per tile, so EVERY thread of
+// the workgroup must call this, a thread without a query of its own with any valid point.  A
+// candidate displaces a best only when strictly nearer, so of two equally distant points the
+// earlier index keeps the better slot: the tie rule the reference has, written this once.
+// (The bests are locals returned by value: through reference parameters they stay in scratch.)
 template <int FORM>
-__global__ __launch_bounds__(NN_BLOCK) void three_nn_kernel(
-    int n, int m, const float *__restrict__ unknown, const float *__restrict__ known,
-    float *__restrict__ dist2, int *__restrict__ idx) {
-  __shared__ float4 kk[NN_TILE];  // (x, y, z, -): one ds_read_b128 broadcast per known point
-  const int bi = blockIdx.y;
-  const int q = blockIdx.x * NN_BLOCK + threadIdx.x;
-  const bool live = q < n;
-  unknown += (size_t)bi * n * 3;
-  known += (size_t)bi * m * 3;
-  const int qq = live ? q : n - 1;
-  const float ux = unknown[qq * 3 + 0], uy = unknown[qq * 3 + 1], uz = unknown[qq * 3 + 2];
+__device__ __forceinline__ ThreeNN three_nn_scan(float ux, float uy, float uz,
+                                                 const float *__restrict__ known, int m, float4 *kk) {
   float b1 = INFINITY, b2 = INFINITY, b3 = INFINITY;
   int i1 = 0, i2 = 0, i3 = 0;
   for (int t0 = 0; t0 < m; t0 += NN_TILE) {
@@ -57,11 +61,27 @@ __global__ __launch_bounds__(NN_BLOCK) void three_nn_kernel(
       }
     }
   }
+  return {b1, b2, b3, i1, i2, i3};
+}
+
+template <int FORM>
+__global__ __launch_bounds__(NN_BLOCK) void three_nn_kernel(
+    int n, int m, const float *__restrict__ unknown, const float *__restrict__ known,
+    float *__restrict__ dist2, int *__restrict__ idx) {
+  __shared__ float4 kk[NN_TILE];  // (x, y, z, -): one ds_read_b128 broadcast per known point
+  const int bi = blockIdx.y;
+  const int q = blockIdx.x * NN_BLOCK + threadIdx.x;
+  const bool live = q < n;
+  unknown += (size_t)bi * n * 3;
+  known += (size_t)bi * m * 3;
+  const int qq = live ? q : n - 1;
+  const float ux = unknown[qq * 3 + 0], uy = unknown[qq * 3 + 1], uz = unknown[qq * 3 + 2];
+  const ThreeNN nn = three_nn_scan<FORM>(ux, uy, uz, known, m, kk);
   if (live) {
     float *od = dist2 + ((size_t)bi * n + q) * 3;
     int *oi = idx + ((size_t)bi * n + q) * 3;
-    od[0] = b1; od[1] = b2; od[2] = b3;
-    oi[0] = i1; oi[1] = i2; oi[2] = i3;
+    od[0] = nn.b1; od[1] = nn.b2; od[2] = nn.b3;
+    oi[0] = nn.i1; oi[1] = nn.i2; oi[2] = nn.i3;
   }
 }
 
@@ -101,37 +121,13 @@ __global__ __launch_bounds__(NN_BLOCK) void grid_taps_kernel(
   const float uy = __fadd_rn(__fadd_rn(__fmul_rn(l[0], -sh), __fmul_rn(l[1], ch)), cy);
   const float uz = __fadd_rn(l[2], cz);
   known += (size_t)bi * m * 3;
-  float b1 = INFINITY, b2 = INFINITY, b3 = INFINITY;
-  int i1 = 0, i2 = 0, i3 = 0;
-  for (int t0 = 0; t0 < m; t0 += NN_TILE) {
-    const int tn = m - t0 < NN_TILE ? m - t0 : NN_TILE;
-    __syncthreads();
-    for (int i = threadIdx.x; i < tn; i += NN_BLOCK)
-      kk[i] = make_float4(known[(t0 + i) * 3 + 0], known[(t0 + i) * 3 + 1],
-                          known[(t0 + i) * 3 + 2], 0.f);
-    __syncthreads();
-#pragma unroll 4
-    for (int i = 0; i < tn; ++i) {
-      const float4 kp = kk[i];
-      const float d = sqdist_form<FORM>(ux - kp.x, uy - kp.y, uz - kp.z);
-      if (d < b3) {
-        const int kidx = t0 + i;
-        if (d < b1) {
-          b3 = b2; i3 = i2; b2 = b1; i2 = i1; b1 = d; i1 = kidx;
-        } else if (d < b2) {
-          b3 = b2; i3 = i2; b2 = d; i2 = kidx;
-        } else {
-          b3 = d; i3 = kidx;
-        }
-      }
-    }
-  }
+  const ThreeNN nn = three_nn_scan<FORM>(ux, uy, uz, known, m, kk);
   if (live) {
     const size_t o = ((size_t)bi * n + q) * 3;
-    const float w1 = 1.f / __fadd_rn(sqrtf(b1), 1e-8f), w2 = 1.f / __fadd_rn(sqrtf(b2), 1e-8f),
-                w3 = 1.f / __fadd_rn(sqrtf(b3), 1e-8f);
+    const float w1 = 1.f / __fadd_rn(sqrtf(nn.b1), 1e-8f), w2 = 1.f / __fadd_rn(sqrtf(nn.b2), 1e-8f),
+                w3 = 1.f / __fadd_rn(sqrtf(nn.b3), 1e-8f);
     const float ws = __fadd_rn(__fadd_rn(w1, w2), w3);
-    idx[o] = i1; idx[o + 1] = i2; idx[o + 2] = i3;
+    idx[o] = nn.i1; idx[o + 1] = nn.i2; idx[o + 2] = nn.i3;
     weight[o] = w1 / ws; weight[o + 1] = w2 / ws; weight[o + 2] = w3 / ws;
     rel[o] = ux - cx; rel[o + 1] = uy - cy; rel[o + 2] = uz - cz;
   }
@@ -399,20 +395,6 @@ __global__ __launch_bounds__(TI_BLOCK) void blend_fwd_generic_kernel(
 constexpr int BL_RUN = 512;  // consecutive queries per workgroup (long runs: the per-workgroup
                              // set-up and the d_wx partial are paid once per run)
 
-__device__ __forceinline__ unsigned bitonic_sort64(unsigned v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const unsigned o = (unsigned)__shfl_xor((int)v, j, 64);
-      const bool up = (lane & k) == 0;           // this block sorts ascending
-      const bool lower = (lane & j) == 0;        // this lane keeps the smaller of the pair
-      v = (up == lower) ? (v < o ? v : o) : (v > o ? v : o);
-    }
-  }
-  return v;
-}
-
 // CPT = c / 64 channels per lane: a wave covers ALL c channels of its 16 queries.
 // BNB: `dy` is the gradient dA of relu(bn(Z)) with Z = this blend's own output (`bnz`, same layout):
 // the BatchNorm + ReLU backward's apply pass runs on the tile load,
@@ -546,7 +528,7 @@ __global__ __launch_bounds__(256, 2) void blend_bwd_rows_kernel(
     // the 48 taps of these 16 queries in seed order: key = seed << 6 | tap
     unsigned key = 0xFFFFFFFFu;
     if (lane < 48) key = ((unsigned)sj[q0 + lane / 3][lane % 3] << 6) | (unsigned)lane;
-    key = bitonic_sort64(key, lane);
+    key = wave_sort64(key, lane);
     int cur = -1;
     float acc[CPT];
 #pragma unroll
@@ -788,13 +770,10 @@ extern "C" int nesie_three_nn_wrapper(int b, int n, int m, const float *unknown,
   if (b == 0 || n == 0) return NESIE_OK;
   NESIE_REQUIRE(unknown && dist2 && idx && (m == 0 || known), W);
   NESIE_REQUIRE(b <= 65535 && (long long)n * 3 < (1ll << 31) && (long long)m * 3 < (1ll << 31), W);
-#define NN(FORM)                                                                          \
-  hipLaunchKernelGGL(three_nn_kernel<FORM>, dim3(cdiv(n, NN_BLOCK), b), dim3(NN_BLOCK), 0, \
-                     (hipStream_t)stream, n, m, unknown, known, dist2, idx)
-  if (distance_form() == 1) NN(1);
-  else if (distance_form() == 2) NN(2);
-  else NN(0);
-#undef NN
+  with_distance_form([&](auto form) {
+    hipLaunchKernelGGL(three_nn_kernel<decltype(form)::value>, dim3(cdiv(n, NN_BLOCK), b), dim3(NN_BLOCK), 0,
+                       (hipStream_t)stream, n, m, unknown, known, dist2, idx);
+  });
   return check_launch(W);
 }
 
@@ -807,14 +786,11 @@ extern "C" int nesie_grid_taps(int b, int kprop, int gp, int m, const float *cen
   if (b == 0 || kprop == 0 || gp == 0) return NESIE_OK;
   NESIE_REQUIRE(m >= 3 && centre && size && heading && mult && plane && known, W);
   NESIE_REQUIRE(idx && weight && rel && b <= 65535 && (long long)kprop * gp * 3 < (1ll << 31), W);
-#define GT(FORM)                                                                                \
-  hipLaunchKernelGGL(grid_taps_kernel<FORM>, dim3(cdiv((long long)kprop * gp, NN_BLOCK), b),     \
-                     dim3(NN_BLOCK), 0, (hipStream_t)stream, kprop, gp, m, centre, size, heading, \
-                     mult, plane, known, idx, weight, rel)
-  if (distance_form() == 1) GT(1);      // (mmcv.ops.three_nn is an nvcc build as well)
-  else if (distance_form() == 2) GT(2);
-  else GT(0);
-#undef GT
+  with_distance_form([&](auto form) {   // (mmcv.ops.three_nn is an nvcc build as well)
+    hipLaunchKernelGGL(grid_taps_kernel<decltype(form)::value>, dim3(cdiv((long long)kprop * gp, NN_BLOCK), b),
+                       dim3(NN_BLOCK), 0, (hipStream_t)stream, kprop, gp, m, centre, size, heading, mult,
+                       plane, known, idx, weight, rel);
+  });
   return check_launch(W);
 }
 

@@ -13,15 +13,11 @@
 // admitted against a stale threshold is merely dropped by the merge: the result is exactly the
 // nsample smallest keys in ascending order.
 //
-// The pending buffer is PRIVATE TO ONE WAVE: its lanes hand keys to each other through volatile
-// LDS without a barrier or fence, which rests on the LDS operations of one wave completing in
-// program order, on `volatile` keeping the compiler from reordering or caching the accesses, and
-// on the branch around them being wave-uniform.  Sharing it between waves, or dropping the
-// `volatile`, needs a barrier.  The carry reads pend[64 + lane] and writes pend[lane], never the
-// region just merged; npend <= 127 fits the 128 entries.
+// The pending buffer is private to one wave and needs no barrier: wave_pend_push (wave_sort.h) says why.
 #include <string.h>
 
 #include "common.h"
+#include "wave_sort.h"
 
 namespace nesie {
 
@@ -31,40 +27,6 @@ constexpr int KNN_MAX = 128;     // two keys per lane
 constexpr unsigned long long KNN_EMPTY = ~0ull;   // larger than every key of a point
 
 typedef unsigned long long knn_key;
-
-// 64-bit twins of bq_sort64 / bq_merge_low64 (ball_query.hip)
-__device__ __forceinline__ knn_key knn_sort64(knn_key v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const knn_key o = __shfl_xor(v, j, 64);
-      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-      v = (up == lower) ? (v < o ? v : o) : (v > o ? v : o);
-    }
-  }
-  return v;
-}
-
-// a bitonic sequence over the lanes -> ascending
-__device__ __forceinline__ knn_key knn_bitonic_finish(knn_key v, int lane) {
-#pragma unroll
-  for (int j = 32; j >= 1; j >>= 1) {
-    const knn_key o = __shfl_xor(v, j, 64);
-    v = ((lane & j) == 0) ? (v < o ? v : o) : (v > o ? v : o);
-  }
-  return v;
-}
-
-// best, add: ascending over the lanes; best <- the 64 smallest of the 128, ascending; with HIGH,
-// add <- the 64 largest, ascending
-template <bool HIGH>
-__device__ __forceinline__ void knn_merge64(knn_key &best, knn_key &add, int lane) {
-  const knn_key rev = __shfl(add, 63 - lane, 64);
-  const knn_key low = best < rev ? best : rev;   // both halves of the split are bitonic
-  if (HIGH) add = knn_bitonic_finish(best < rev ? rev : best, lane);
-  best = knn_bitonic_finish(low, lane);
-}
 
 template <int FORM, bool WIDE>
 __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(
@@ -86,13 +48,13 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(
   int npend = 0;
 
   auto merge = [&](knn_key v) {
-    v = knn_sort64(v, lane);
+    v = wave_sort64(v, lane);
     if (WIDE) {
-      knn_merge64<true>(lo, v, lane);
-      knn_merge64<false>(hi, v, lane);
+      wave_merge64<true>(lo, v, lane);
+      wave_merge64<false>(hi, v, lane);
       kth = __shfl(hi, nsample - 65, 64);
     } else {
-      knn_merge64<false>(lo, v, lane);
+      wave_merge64<false>(lo, v, lane);
       kth = __shfl(lo, nsample - 1, 64);
     }
   };
@@ -107,24 +69,11 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(
       const int p = s + lane;  // < KNN_TILE; past cnt the tile holds stale values that are not used
       const float d2 = sqdist_form<FORM>(cx - tile[p * 3 + 0], cy - tile[p * 3 + 1], cz - tile[p * 3 + 2]);
       const knn_key key = p < cnt ? ((knn_key)__float_as_uint(d2) << 32) | (unsigned)(base + p) : KNN_EMPTY;
-      const bool cand = key < kth;
-      const unsigned long long hm = __builtin_amdgcn_ballot_w64(cand);
-      if (hm) {
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32),
-                                                   __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0));
-        if (cand) pend[npend + rank] = key;
-        npend += __popcll(hm);
-        if (npend >= 64) {  // npend < 128 always: at most 63 carried + 64 new
-          merge(pend[lane]);
-          const knn_key carry = pend[64 + lane];
-          npend -= 64;
-          if (lane < npend) pend[lane] = carry;
-        }
-      }
+      wave_pend_push(pend, npend, lane, key < kth, key, merge);
     }
   }
   if (!live) return;
-  if (npend > 0) merge(lane < npend ? pend[lane] : KNN_EMPTY);
+  wave_pend_flush(pend, npend, lane, KNN_EMPTY, merge);
 
   // a slot no point reached (n < nsample) keeps the state the reference's heap starts from
   // (knn_cuda.cu:74-77): index 0, distance 1e10
@@ -170,19 +119,15 @@ extern "C" int nesie_knn_wrapper(int b, int n, int m, int nsample, const float *
   NESIE_REQUIRE((long long)n * 3 < (1ll << 31), W);
   const long long groups = cdiv(m, KNN_WAVES);
   NESIE_REQUIRE(groups * b < (1ll << 31), W);
-#define KNN(FORM, WIDE)                                                                          \
-  hipLaunchKernelGGL((knn_kernel<FORM, WIDE>), dim3((unsigned)(groups * b)), dim3(KNN_WAVES * 64), \
-                     0, (hipStream_t)stream, b, n, m, nsample, xyz, new_xyz, idx, dist2)
-  const int form = distance_form();
-  if (nsample <= 64) {
-    if (form == 1) KNN(1, false);
-    else if (form == 2) KNN(2, false);
-    else KNN(0, false);
-  } else {
-    if (form == 1) KNN(1, true);
-    else if (form == 2) KNN(2, true);
-    else KNN(0, true);
-  }
-#undef KNN
+  const dim3 grid((unsigned)(groups * b)), block(KNN_WAVES * 64);
+  with_distance_form([&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if (nsample <= 64)
+      hipLaunchKernelGGL((knn_kernel<FORM, false>), grid, block, 0, (hipStream_t)stream, b, n, m, nsample,
+                         xyz, new_xyz, idx, dist2);
+    else
+      hipLaunchKernelGGL((knn_kernel<FORM, true>), grid, block, 0, (hipStream_t)stream, b, n, m, nsample,
+                         xyz, new_xyz, idx, dist2);
+  });
   return check_launch(W);
 }

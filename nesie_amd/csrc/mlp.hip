@@ -9,17 +9,6 @@ namespace nesie {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-
-// sum over the 32 lanes of each half-wave (result in every lane of the half)
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-  v += __shfl_xor(v, 16, 64);
-  return v;
-}
-
 }  // namespace nesie
 
 using namespace nesie;
@@ -508,14 +497,14 @@ __global__ __launch_bounds__(256) void mlp_stream_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const float q = half_wave_sum(qrow[i][r]);
+        const float q = wave_sum_dpp<32>(qrow[i][r]);
         if (l32 == 0) sq_w[wave][m] = q;
       }
     // column sums of the operand per k, then sum(y)[m] = sum_k W[m][k] * colsum[k]
     __shared__ float colsum[2 * KP];
 #pragma unroll
     for (int kp = 0; kp < KP; ++kp) {
-      const float t = half_wave_sum(ax[kp]);
+      const float t = wave_sum_dpp<32>(ax[kp]);
       if (l32 == 0) cs_w[wave][kp * 2 + half] = t;
     }
     __syncthreads();

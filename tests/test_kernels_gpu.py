@@ -1015,6 +1015,39 @@ def test_grid_taps_equal_three_nn_on_the_same_points(hip_device, m, dups):
     torch.testing.assert_close(weight, w / w.sum(-1, keepdim=True), rtol=1e-6, atol=1e-7)
 
 
+@pytest.mark.parametrize("form", [1, 2])
+def test_grid_taps_equal_three_nn_in_the_fused_distance_forms(hip_device, form):
+    """The same comparison with nesie_set_distance_form(1 / 2), which no other test makes for the
+    grid taps: m = 1030 seeds (six past one LDS tile), the second half exact duplicates of the
+    first.  grid_taps_kernel and three_nn_kernel share the 3-nearest scan (three_nn_scan), so equal
+    indices here pin the launcher's dispatch on the form and the kernel's prologue, not the scan;
+    the scan in forms 1 and 2 is pinned against the oracle through three_nn."""
+    from nesie_amd.mmdet3d_ops import three_nn
+    g = torch.Generator().manual_seed(1030 + form)
+    B, K, gp, m = 1, 4, 8, 1030
+    known = torch.rand(B, m, 3, generator=g) * torch.tensor([8.0, 6.0, 2.5])
+    known[:, m // 2:] = known[:, :m - m // 2]      # exact duplicates: equal distances, index decides
+    centre = torch.rand(B, K, 3, generator=g) * torch.tensor([8.0, 6.0, 2.5])
+    size = 0.2 + torch.rand(B, K, 3, generator=g) * 2
+    heading = (torch.rand(B, K, generator=g) - 0.5) * 6
+    mult = torch.rand(gp, 3, generator=g) * 2 - 1
+    plane = torch.zeros(gp, 3)
+    dev = lambda t: t.to(hip_device).contiguous()   # noqa: E731
+    hip = kernels.backend_for(dev(known))
+    try:
+        hip.set_distance_form(form)
+        assert hip.get_distance_form() == form
+        idx, _, rel = hip.grid_taps(dev(centre), dev(size), dev(heading), dev(mult), dev(plane), dev(known))
+        world = rel + dev(centre).repeat_interleave(gp, 1)
+        _, ref_idx = three_nn(world.contiguous(), dev(known))
+    finally:
+        hip.set_distance_form(0)
+    assert hip.get_distance_form() == 0
+    assert torch.equal(idx, ref_idx)
+    # the nearest seed and its duplicate are equally near: the earlier index takes the better slot
+    assert torch.equal(idx[..., 1], idx[..., 0] + m // 2)
+
+
 def test_flat_adamw_with_clipping_matches_torch(hip_device):
     """dp.FlatAdamW (nesie_flat_adamw_step) == clip_grad_norm_ + torch.optim.AdamW, several steps,
     with and without the clip active."""
