@@ -185,14 +185,11 @@ extern "C" int nesie_aa_iou3d_paired_forward(int n, const float *box1, const flo
   A.mode = mode; A.eps = eps;
   const dim3 grid(cdiv(n, 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (jac1 && jac2)
-    hipLaunchKernelGGL((aa_paired_kernel<true, true>), grid, block, 0, s, A, out, jac1, jac2);
-  else if (jac1)
-    hipLaunchKernelGGL((aa_paired_kernel<true, false>), grid, block, 0, s, A, out, jac1, jac2);
-  else if (jac2)
-    hipLaunchKernelGGL((aa_paired_kernel<false, true>), grid, block, 0, s, A, out, jac1, jac2);
-  else
-    hipLaunchKernelGGL((aa_paired_kernel<false, false>), grid, block, 0, s, A, out, jac1, jac2);
+  with_bool(jac1 != nullptr, [&](auto J1) {
+    with_bool(jac2 != nullptr, [&](auto J2) {
+      hipLaunchKernelGGL((aa_paired_kernel<J1(), J2()>), grid, block, 0, s, A, out, jac1, jac2);
+    });
+  });
   return check_launch(W);
 }
 

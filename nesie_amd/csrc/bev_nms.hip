@@ -216,11 +216,6 @@ __global__ __launch_bounds__(64) void bev_nms_walk_kernel(
   if (lane == 0) count[s] = np;
 }
 
-__global__ __launch_bounds__(256) void bev_nms_zero_kernel(int n, int *__restrict__ p) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 }  // namespace nesie
 
 using namespace nesie;
@@ -240,7 +235,7 @@ extern "C" int nesie_bev_nms(int n, int s, int max_seg, const float *boxes, cons
   NESIE_REQUIRE(count, W);
   hipStream_t st = (hipStream_t)stream;
   if (n == 0 || max_seg == 0) {
-    hipLaunchKernelGGL(bev_nms_zero_kernel, dim3(cdiv(s, 256)), dim3(256), 0, st, s, count);
+    zero_i32(count, s, st);
     return check_launch(W);
   }
   NESIE_REQUIRE(boxes && scores && offsets && keep && workspace, W);
@@ -253,12 +248,10 @@ extern "C" int nesie_bev_nms(int n, int s, int max_seg, const float *boxes, cons
   int *order = (int *)(sboxes + (size_t)n * 5);
   hipLaunchKernelGGL(bev_nms_rank_kernel, dim3(words, s), dim3(BNMS_RANK_BLOCK), 0, st, n,
                      max_seg, boxes, scores, valid, offsets, sboxes, order);
-  if (rotated)
-    hipLaunchKernelGGL(bev_nms_mask_kernel<true>, dim3(words, words, s), dim3(64), 0, st, n,
-                       max_seg, words, sboxes, order, valid, offsets, thr, mask);
-  else
-    hipLaunchKernelGGL(bev_nms_mask_kernel<false>, dim3(words, words, s), dim3(64), 0, st, n,
-                       max_seg, words, sboxes, order, valid, offsets, thr, mask);
+  with_bool(rotated, [&](auto ROT) {
+    hipLaunchKernelGGL(bev_nms_mask_kernel<ROT()>, dim3(words, words, s), dim3(64), 0, st, n, max_seg, words,
+                       sboxes, order, valid, offsets, thr, mask);
+  });
   hipLaunchKernelGGL(bev_nms_walk_kernel, dim3(s), dim3(64), 0, st, n, max_seg, words, order,
                      valid, offsets, mask, keep, count);
   return check_launch(W);

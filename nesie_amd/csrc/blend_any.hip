@@ -255,12 +255,10 @@ extern "C" int nesie_blend_conv_backward_any(int b, int c, int m, int n, const f
   const int nruns = cdiv(per_seg, BA_RUN), ncblk = cdiv(c, BA_C);
   NESIE_REQUIRE((long long)nruns * b * segs * ncblk < (1ll << 31) && (long long)segs * c * 3 < (1ll << 31), W);
   const dim3 grid((unsigned)(nruns * b * segs * ncblk));
-  if (bnb)
-    hipLaunchKernelGGL(blend_any_rows_kernel<true>, grid, dim3(256), 0, s, c, n, segs, seg_len, dy,
-                       rel, z, bnb, dzt, d_wx ? part : (float *)nullptr, b, nruns, ncblk);
-  else
-    hipLaunchKernelGGL(blend_any_rows_kernel<false>, grid, dim3(256), 0, s, c, n, segs, seg_len, dy,
-                       rel, z, bnb, dzt, d_wx ? part : (float *)nullptr, b, nruns, ncblk);
+  with_bool(bnb != nullptr, [&](auto BNB) {
+    hipLaunchKernelGGL(blend_any_rows_kernel<BNB()>, grid, dim3(256), 0, s, c, n, segs, seg_len, dy, rel, z, bnb,
+                       dzt, d_wx ? part : (float *)nullptr, b, nruns, ncblk);
+  });
   NESIE_LAUNCHED(W);
   if (d_wx)
     hipLaunchKernelGGL(blend_any_wx_kernel, dim3((unsigned)cdiv((long long)segs * c * 3, 256)),

@@ -510,10 +510,11 @@ extern "C" int nesie_bn_relu_forward(int b, int c, long long p, const float *x,
                      pre_partial ? pre_partial : partial, gamma, beta,
                      running_mean, running_var, momentum, eps, save_mean, save_invstd, coef};
   const bool nt = bn_use_nt((long long)b * c * p);
-#define L(R, N) hipLaunchKernelGGL((bn_apply_kernel<R, N>), grid, dim3(BN_BLOCK), 0, s, c, p, x, row_bias, group, fin, y)
-  if (relu) { if (nt) L(true, true); else L(true, false); }
-  else { if (nt) L(false, true); else L(false, false); }
-#undef L
+  with_bool(relu, [&](auto R) {
+    with_bool(nt, [&](auto N) {
+      hipLaunchKernelGGL((bn_apply_kernel<R(), N()>), grid, dim3(BN_BLOCK), 0, s, c, p, x, row_bias, group, fin, y);
+    });
+  });
   return check_launch(W);
 }
 
@@ -545,19 +546,17 @@ extern "C" int nesie_bn_relu_backward(int b, int c, long long p, const float *dy
   float *partial = (float *)workspace, *coef = partial + (size_t)c * nslice * 2;
   dim3 grid(sp, c, b);
   const bool nt = bn_use_nt((long long)b * c * p);
-#define LR(R, N) hipLaunchKernelGGL((bn_bwd_reduce_kernel<R, N>), grid, dim3(BN_BLOCK), 0, s, c, p, sp, dy, \
-                                    x, y, save_mean, save_invstd, gamma, beta, row_bias, group, partial, \
-                                    raw ? fwd_coef : (const float *)nullptr, fwd_coef)
-  if (relu) { if (nt) LR(true, true); else LR(true, false); }
-  else { if (nt) LR(false, true); else LR(false, false); }
-#undef LR
   const BnBwdFin fin{nslice, (double)b * (double)p, partial, gamma, save_invstd ? save_invstd : fwd_coef + 3, dgamma, dbeta, save_invstd ? 1 : 4};
   (void)coef;
-#define LA(R, N) hipLaunchKernelGGL((bn_bwd_apply_kernel<R, N>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x, \
-                                    fwd_coef, fin, row_bias, group, d_row_bias, dx, raw)
-  if (relu) { if (nt) LA(true, true); else LA(true, false); }
-  else { if (nt) LA(false, true); else LA(false, false); }
-#undef LA
+  with_bool(relu, [&](auto R) {
+    with_bool(nt, [&](auto N) {
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<R(), N()>), grid, dim3(BN_BLOCK), 0, s, c, p, sp, dy, x, y,
+                         save_mean, save_invstd, gamma, beta, row_bias, group, partial,
+                         raw ? fwd_coef : (const float *)nullptr, fwd_coef);
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<R(), N()>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x, fwd_coef,
+                         fin, row_bias, group, d_row_bias, dx, raw);
+    });
+  });
   return check_launch(W);
 }
 
@@ -584,13 +583,22 @@ extern "C" int nesie_bn_relu_backward_apply(int b, int c, long long p, const flo
   dim3 grid(bn_sp(p), c, b);
   const bool nt = bn_use_nt((long long)b * c * p);
   const BnBwdFin fin{nslice, (double)b * (double)p, partial, gamma, save_invstd ? save_invstd : fwd_coef + 3, dgamma, dbeta, save_invstd ? 1 : 4};
-  if (nt)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x,
+  with_bool(nt, [&](auto N) {
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, N()>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x,
                        fwd_coef, fin, (const float *)nullptr, group, d_row_bias, dx, 1);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x,
-                       fwd_coef, fin, (const float *)nullptr, group, d_row_bias, dx, 1);
+  });
   return check_launch(W);
+}
+
+// the pooled forward of ns = 4 * lpr samples a row (bn_pool_dims: a power of two in 4..64); the
+// training and the evaluation entry point differ in where coef comes from
+static bool bn_pool_fwd_launch(dim3 grid, hipStream_t s, long long rows, int m, int c, int ns, const float *x,
+                               const float *coef, float *pooled, uint8_t *argmax) {
+  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
+  return with_int<1, 2, 4, 8, 16>(ns / 4, [&](auto LPR) {
+    hipLaunchKernelGGL(bn_pool_fwd_kernel<LPR()>, grid, dim3(256), 0, s, rows, m, c, (const float4 *)x, coef,
+                       pooled, argmax, nt);
+  });
 }
 
 static int bn_pool_dims(const char *W, int m, int ns) {
@@ -631,12 +639,7 @@ extern "C" int nesie_bn_relu_maxpool_forward(int b, int c, int m, int ns, const 
   const int lpr = ns / 4;
   NESIE_REQUIRE((long long)b * c <= 65535 && (long long)m * lpr < (1ll << 30), W);
   const dim3 grid((unsigned)cdiv((long long)m * lpr, 256), (unsigned)(b * c));
-#define L(N) hipLaunchKernelGGL(bn_pool_fwd_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
-                                (const float4 *)x, fwd_coef, pooled, argmax, nt)
-  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
-  if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
-  else if (lpr == 8) L(8); else L(16);
-#undef L
+  NESIE_REQUIRE(bn_pool_fwd_launch(grid, s, rows, m, c, ns, x, fwd_coef, pooled, argmax), W);
   return check_launch(W);
 }
 
@@ -668,13 +671,12 @@ extern "C" int nesie_bn_relu_maxpool_backward(int b, int c, int m, int ns,
   const int lpr = ns / 4;
   NESIE_REQUIRE((long long)b * c <= 65535 && (long long)m * lpr < (1ll << 30), W);
   const dim3 grid((unsigned)cdiv((long long)m * lpr, 256), (unsigned)(b * c));
-#define L(N) hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
-                                (const float4 *)x, grad_pooled, pooled, argmax, fwd_coef, coef, \
-                                (float4 *)dx, nt)
   const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
-  if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
-  else if (lpr == 8) L(8); else L(16);
-#undef L
+  const bool built = with_int<1, 2, 4, 8, 16>(lpr, [&](auto LPR) {
+    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<LPR()>, grid, dim3(256), 0, s, rows, m, c, (const float4 *)x,
+                       grad_pooled, pooled, argmax, fwd_coef, coef, (float4 *)dx, nt);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 
@@ -722,10 +724,11 @@ extern "C" int nesie_affine_relu_forward(int b, int c, long long p, const float 
   const dim3 grid(bn_sp(p), c, b);
   hipStream_t s = (hipStream_t)stream;
   const bool nt = bn_use_nt((long long)b * c * p);
-#define L(R, N) hipLaunchKernelGGL((affine_apply_kernel<R, N>), grid, dim3(BN_BLOCK), 0, s, c, p, x, row_bias, group, coef, y)
-  if (relu) { if (nt) L(true, true); else L(true, false); }
-  else { if (nt) L(false, true); else L(false, false); }
-#undef L
+  with_bool(relu, [&](auto R) {
+    with_bool(nt, [&](auto N) {
+      hipLaunchKernelGGL((affine_apply_kernel<R(), N()>), grid, dim3(BN_BLOCK), 0, s, c, p, x, row_bias, group, coef, y);
+    });
+  });
   return check_launch(W);
 }
 
@@ -745,11 +748,6 @@ extern "C" int nesie_affine_relu_maxpool_forward(int b, int c, int m, int ns, co
   NESIE_REQUIRE((long long)b * c <= 65535 && (long long)m * lpr < (1ll << 30), W);
   const dim3 grid((unsigned)cdiv((long long)m * lpr, 256), (unsigned)(b * c));
   hipStream_t s = (hipStream_t)stream;
-  const int nt = stream_nt(rows * ns * 4) ? 1 : 0;
-#define L(N) hipLaunchKernelGGL(bn_pool_fwd_kernel<N>, grid, dim3(256), 0, s, rows, m, c, \
-                                (const float4 *)x, coef, pooled, argmax, nt)
-  if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
-  else if (lpr == 8) L(8); else L(16);
-#undef L
+  NESIE_REQUIRE(bn_pool_fwd_launch(grid, s, rows, m, c, ns, x, coef, pooled, argmax), W);
   return check_launch(W);
 }

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "../../include/nesie_ops.h"
+#include "dispatch.h"
 
 namespace nesie {
 
@@ -40,6 +41,10 @@ inline int check_launch(const char *what) {
     if (e_ != NESIE_OK) return e_;                  \
   } while (0)
 
+// p[0 .. n) = 0 as a launch (nesie_lib.hip says why not hipMemsetAsync): for a buffer that the next
+// kernel adds into
+void zero_i32(int *p, int n, hipStream_t s);
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -71,15 +76,28 @@ __device__ __forceinline__ float sqdist_form(float dx, float dy, float dz) {
   return sqdist_nofma(dx, dy, dz);
 }
 
-// Calls f(std::integral_constant<int, FORM>()) with FORM = distance_form(): a launcher writes its
-// kernel<decltype(form)::value> once, inside a generic lambda.
+// with_int over FORM = distance_form() (dispatch.h): a launcher writes its kernel<FORM()> once,
+// inside a generic lambda.
 template <typename F>
 inline void with_distance_form(F &&f) {
-  switch (distance_form()) {
-    case 1: f(std::integral_constant<int, 1>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    default: f(std::integral_constant<int, 0>()); break;
+  const int form = distance_form();
+  with_int<0, 1, 2>(form == 1 || form == 2 ? form : 0, f);
+}
+
+// Launches Kern with `lds` bytes of dynamic LDS.  One rule for every kernel that may need more
+// than the 64 KB a kernel gets by default: the limit requested so far is kept per kernel
+// instantiation (the static belongs to this template's instantiation; 64 KB at first) and is
+// raised whenever max(lds, CEIL) exceeds it.  CEIL is for a site that knows its kernel's maximum:
+// the first launch then asks for it, whatever its own size, and no later one asks again.
+template <auto Kern, size_t CEIL = 0, typename... Args>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static size_t limit = 65536;
+  const size_t want = lds > CEIL ? lds : CEIL;
+  if (want > limit) {
+    (void)hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+    limit = want;
   }
+  hipLaunchKernelGGL(Kern, grid, block, lds, s, args...);
 }
 
 // 64-bit max across the 64 lanes of a wave (result valid in every lane).

@@ -186,15 +186,14 @@ static inline bool fl_vec(const fl_problem &q, const void *a, const void *b) {
          (q.sw_mode != 2 || aligned16(q.sample_weight));
 }
 
-#define FL_LAUNCH(MODE, VEC, GRID, ...)                                                            \
-  do {                                                                                             \
-    if (VEC)                                                                                       \
-      hipLaunchKernelGGL((focal_kernel<MODE, true>), dim3((unsigned)(GRID)), dim3(FL_BLOCK), 0,    \
-                         (hipStream_t)stream, __VA_ARGS__);                                        \
-    else                                                                                           \
-      hipLaunchKernelGGL((focal_kernel<MODE, false>), dim3((unsigned)(GRID)), dim3(FL_BLOCK), 0,   \
-                         (hipStream_t)stream, __VA_ARGS__);                                        \
-  } while (0)
+// one launch of focal_kernel<MODE, vec> over `grid` workgroups
+template <int MODE, typename... Args>
+static void fl_launch(bool vec, int grid, void *stream, Args... args) {
+  with_bool(vec, [&](auto VEC) {
+    hipLaunchKernelGGL((focal_kernel<MODE, VEC()>), dim3((unsigned)grid), dim3(FL_BLOCK), 0, (hipStream_t)stream,
+                       args...);
+  });
+}
 
 }  // namespace nesie
 
@@ -214,8 +213,8 @@ extern "C" int nesie_sigmoid_focal_loss_forward(int n, int c, const float *x, co
   q.alpha = alpha;
   const float *none = nullptr;
   float *no_partial = nullptr;
-  FL_LAUNCH(FL_NONE, fl_vec(q, loss, nullptr), cdiv(q.total, FL_CHUNK), q, none, none, scale, none,
-            loss, no_partial);
+  fl_launch<FL_NONE>(fl_vec(q, loss, nullptr), cdiv(q.total, FL_CHUNK), stream, q, none, none, scale, none, loss,
+                     no_partial);
   return check_launch(W);
 }
 
@@ -249,8 +248,7 @@ extern "C" int nesie_sigmoid_focal_loss_forward_sum(int n, int c, const float *x
   }
   const float *none = nullptr;
   float *partial = (float *)workspace;
-  FL_LAUNCH(FL_SUM, fl_vec(q, nullptr, nullptr), parts, q, none, none, scale, scale_dev, out,
-            partial);
+  fl_launch<FL_SUM>(fl_vec(q, nullptr, nullptr), parts, stream, q, none, none, scale, scale_dev, out, partial);
   int st2 = check_launch(W);
   if (st2 || parts == 1) return st2;
   hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(FL_BLOCK), 0, (hipStream_t)stream, parts,
@@ -275,7 +273,7 @@ extern "C" int nesie_sigmoid_focal_loss_backward(int n, int c, const float *x, c
   NESIE_REQUIRE((grad_out != nullptr) != (grad_scalar != nullptr), W);
   q.alpha = alpha;
   float *no_partial = nullptr;
-  FL_LAUNCH(FL_GRAD, fl_vec(q, grad_x, grad_out), cdiv(q.total, FL_CHUNK), q, grad_out, grad_scalar,
-            scale, scale_dev, grad_x, no_partial);
+  fl_launch<FL_GRAD>(fl_vec(q, grad_x, grad_out), cdiv(q.total, FL_CHUNK), stream, q, grad_out, grad_scalar, scale,
+                     scale_dev, grad_x, no_partial);
   return check_launch(W);
 }

@@ -645,10 +645,9 @@ static int fps_launch(int b, int n, int m, const float *xyz, float *temp, int *i
   const int L = fps_ref_log2_block(n);
   dim3 grid(b);
   if (distance_form() != 0) {   // checking aid (common.h, sqdist_form): the plain kernel only
-    if (distance_form() == 1)
-      hipLaunchKernelGGL((fps_generic_kernel<false, 1>), grid, dim3(1024), 0, s, n, m, L, xyz, temp, idx);
-    else
-      hipLaunchKernelGGL((fps_generic_kernel<false, 2>), grid, dim3(1024), 0, s, n, m, L, xyz, temp, idx);
+    with_int<1, 2>(distance_form(), [&](auto FORM) {
+      hipLaunchKernelGGL((fps_generic_kernel<false, FORM()>), grid, dim3(1024), 0, s, n, m, L, xyz, temp, idx);
+    });
     return check_launch(W);
   }
 #define REG(BLK, P) \
@@ -661,23 +660,14 @@ static int fps_launch(int b, int n, int m, const float *xyz, float *temp, int *i
     float4 *wp = (float4 *)workspace;
     unsigned *wo = (unsigned *)((char *)workspace + (size_t)b * n * 16);
     const size_t lt_bytes = (size_t)n * 4 > (FPS_CELLS + 1024) * 4 ? (size_t)n * 4 : (FPS_CELLS + 1024) * 4;
-#define PRUNED_LDS(FULL)                                                                         \
-  do {                                                                                           \
-    auto kern = fps_pruned_kernel<16, true, FULL>;                                               \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      (void)hipFuncSetAttribute((const void *)kern,                                              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160768);             \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lt_bytes, s, n, m, xyz, temp, idx, wp, wo);    \
-  } while (0)
     if (!fps_lds_mode(n))
       hipLaunchKernelGGL((fps_pruned_kernel<16, false, false>), grid, dim3(16 * 64), 0, s, n, m, xyz,
                          temp, idx, wp, wo);
-    else if (n % 64 == 0) PRUNED_LDS(true);
-    else PRUNED_LDS(false);
-#undef PRUNED_LDS
+    else
+      with_bool(n % 64 == 0, [&](auto FULL) {
+        launch_lds<fps_pruned_kernel<16, true, FULL()>, 160768>(grid, dim3(16 * 64), lt_bytes, s, n, m, xyz, temp,
+                                                                idx, wp, wo);
+      });
     return check_launch(W);
   }
   if (n <= 64) REG(64, 1);

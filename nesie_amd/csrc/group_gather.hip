@@ -365,20 +365,13 @@ static bool launch_group_bwd_csr_rows(int b, int c, int n, long long e_total, lo
   while (ch > 1 && (need(ch) > LDS_MAX || (long long)cdiv(c, ch) * b < 256)) ch >>= 1;
   const size_t lds = (size_t)need(ch);
   const dim3 grid(cdiv(c, ch), b);
-#define GRL(CH, ED)                                                                                     \
-  do {                                                                                                  \
-    static bool attr = false;                                                                           \
-    if (!attr) {                                                                                        \
-      (void)hipFuncSetAttribute((const void *)group_bwd_csr_rows_kernel<CH, ED>,                        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);              \
-      attr = true;                                                                                      \
-    }                                                                                                   \
-    hipLaunchKernelGGL((group_bwd_csr_rows_kernel<CH, ED>), grid, dim3(GR_BLOCK), lds, s, c, n, (int)e_total, \
-                       gstride, ediv, grad_out, weight, order, src, grad_points);                       \
-  } while (0)
-  if (ediv == 1) { if (ch == 8) GRL(8, 1); else if (ch == 4) GRL(4, 1); else if (ch == 2) GRL(2, 1); else GRL(1, 1); }
-  else { if (ch == 8) GRL(8, 3); else if (ch == 4) GRL(4, 3); else if (ch == 2) GRL(2, 3); else GRL(1, 3); }
-#undef GRL
+  with_int<1, 3>(ediv, [&](auto ED) {
+    with_int<1, 2, 4, 8>(ch, [&](auto CH) {
+      launch_lds<group_bwd_csr_rows_kernel<CH(), ED()>, (size_t)LDS_MAX>(grid, dim3(GR_BLOCK), lds, s, c, n, (int)e_total,
+                                                                         gstride, ediv, grad_out, weight, order, src,
+                                                                         grad_points);
+    });
+  });
   return true;
 }
 

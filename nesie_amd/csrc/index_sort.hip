@@ -381,14 +381,8 @@ int launch_inverted_index(int b, int n, long long e_total, const int *idx, int *
   NESIE_REQUIRE(idx && order && sources && scratch, W);
   if (n <= II_STABLE_N) {               // stable counting sort: ascending runs without a ranking pass
     const size_t lds = ((size_t)II_WAVES * n + II_WAVES) * sizeof(int);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void *)inverted_index_stable_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)II_WAVES * II_STABLE_N + II_WAVES) * sizeof(int)));
-      attr = true;
-    }
-    hipLaunchKernelGGL(inverted_index_stable_kernel, dim3(b), dim3(II_BLOCK), lds, s, n, (int)e_total, idx,
-                       order, sources);
+    launch_lds<inverted_index_stable_kernel, ((size_t)II_WAVES * II_STABLE_N + II_WAVES) * sizeof(int)>(
+        dim3(b), dim3(II_BLOCK), lds, s, n, (int)e_total, idx, order, sources);
     return check_launch(W);
   }
   const int windows = cdiv(n, II_WINDOW);

@@ -829,21 +829,13 @@ static void blend_fwd_launch(int chunks, int cb, int b, int c, int m, int n, int
   constexpr int CW = CPT * 64;
   const size_t lds = (size_t)CW * (BF_LD + 4 * 2) * sizeof(float);
   const dim3 grid((unsigned)((n / TS_Q) * b), (unsigned)chunks);
-#define BF(WXF, STF)                                                                              \
-  do {                                                                                            \
-    static bool attr = false;                                                                     \
-    if (!attr) {                                                                                  \
-      (void)hipFuncSetAttribute((const void *)blend_fwd_kernel<CPT, WXF, STF>,                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
-      attr = true;                                                                                \
-    }                                                                                             \
-    hipLaunchKernelGGL((blend_fwd_kernel<CPT, WXF, STF>), grid, dim3(256), lds, s, c, cb, m, n,   \
-                       segs, seg_len, c_total, c_offset, pitch, seg_off, table, idx, weight, rel, \
-                       wx, out, stat_partial, b);                                                 \
-  } while (0)
-  if (wx) { if (stat_partial) BF(true, true); else BF(true, false); }
-  else { if (stat_partial) BF(false, true); else BF(false, false); }
-#undef BF
+  with_bool(wx != nullptr, [&](auto WXF) {
+    with_bool(stat_partial != nullptr, [&](auto STF) {
+      launch_lds<blend_fwd_kernel<CPT, WXF(), STF()>>(grid, dim3(256), lds, s, c, cb, m, n, segs, seg_len, c_total,
+                                                      c_offset, pitch, seg_off, table, idx, weight, rel, wx, out,
+                                                      stat_partial, b);
+    });
+  });
 }
 
 extern "C" int nesie_blend_conv_forward(int b, int c, int m, int n, const float *table,
@@ -867,10 +859,10 @@ extern "C" int nesie_blend_conv_forward(int b, int c, int m, int n, const float 
     blend_fwd_launch<4>(c / 256, 0, b, c, m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table,
                         idx, weight, rel, wx, out, stat_partial, (hipStream_t)stream);
     const int cb = c / 256 * 256, left = (c - cb) / 64;
-#define REST(N) blend_fwd_launch<N>(1, cb, b, c, m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table, \
-                                    idx, weight, rel, wx, out, stat_partial, (hipStream_t)stream)
-    if (left == 1) REST(1); else if (left == 2) REST(2); else if (left == 3) REST(3);
-#undef REST
+    with_int<1, 2, 3>(left, [&](auto CPT) {   // (0: nothing remains)
+      blend_fwd_launch<CPT()>(1, cb, b, c, m, n, segs, seg_len, c_total, c_offset, pitch, seg_off, table, idx,
+                              weight, rel, wx, out, stat_partial, (hipStream_t)stream);
+    });
   } else
     hipLaunchKernelGGL(blend_fwd_generic_kernel, dim3(cdiv(n, TI_BLOCK), cdiv(c, TI_CH), b),
                        dim3(TI_BLOCK), 0, (hipStream_t)stream, c, m, n, segs, seg_len, c_total,
@@ -916,62 +908,40 @@ static int blend_conv_backward_impl(const char *W, int b, int c, int m, int n, c
   NESIE_REQUIRE((long long)nruns * b * segs < (1ll << 31), W);
   const dim3 grid((unsigned)(nruns * b * segs));
   hipStream_t s = (hipStream_t)stream;
-  if (workspace) {   // STAGED: no float atomics, d_table written (not accumulated), reproducible
+  // STAGED (workspace): no float atomics, d_table written (not accumulated), reproducible
+  float *stage = nullptr;
+  int *slot_seed = nullptr, *order = nullptr, *offs = nullptr;
+  const int groups_per_face = per_seg / 16, slots_per_face = groups_per_face * BL_SLOTS;
+  const int nchunk = blend_index_chunks(n, segs);
+  if (workspace) {
     const size_t slots = blend_stage_slots(b, n, segs);
     NESIE_REQUIRE(workspace_bytes >= nesie_blend_conv_backward_workspace_bytes(b, c, n, segs), W);
     NESIE_REQUIRE(((uintptr_t)workspace & 15) == 0 && m + 1 <= SI_MAX_BINS, W);     // (the index: <= 2048 bins)
     NESIE_REQUIRE(pitch % 4 == 0 && seg_off % 4 == 0 && ((uintptr_t)d_table & 15) == 0, W);   // (vector row stores)
-    const int groups_per_face = per_seg / 16, slots_per_face = groups_per_face * BL_SLOTS;
-    const int nchunk = blend_index_chunks(n, segs);
     NESIE_REQUIRE(nchunk <= 64 && (long long)b * segs * nchunk < (1ll << 31) &&
                   (long long)b * segs * m < (1ll << 33), W);
-    float *stage = (float *)workspace;
-    int *slot_seed = (int *)(stage + slots * c), *order = slot_seed + slots,
-        *offs = order + (size_t)b * segs * nchunk * SI_GROUPS * BL_SLOTS;
-#define LS(N)                                                                                      \
-  do {                                                                                             \
-    if (bnb)                                                                                       \
-      hipLaunchKernelGGL((blend_bwd_rows_kernel<N, true, true>), grid, dim3(256), 0, s,            \
-                         m, n, segs, seg_len, pitch, seg_off, dy, idx, weight, rel, d_table, d_wx, \
-                         b, nruns, bnz, bnb, stage, slot_seed);                                    \
-    else                                                                                           \
-      hipLaunchKernelGGL((blend_bwd_rows_kernel<N, false, true>), grid, dim3(256), 0, s,           \
-                         m, n, segs, seg_len, pitch, seg_off, dy, idx, weight, rel, d_table, d_wx, \
-                         b, nruns, bnz, bnb, stage, slot_seed);                                    \
-  } while (0)
-    if (c == 64) LS(1); else if (c == 128) LS(2); else if (c == 192) LS(3); else LS(4);
-#undef LS
-    {
-      const size_t lds = ((size_t)SI_WAVES * m + SI_WAVES) * sizeof(int);
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void *)blend_slot_index_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(((size_t)SI_WAVES * SI_MAX_BINS + SI_WAVES) * sizeof(int)));
-        attr = true;
-      }
-      hipLaunchKernelGGL(blend_slot_index_kernel, dim3((unsigned)(b * segs * nchunk)), dim3(SI_BLOCK), lds, s,
-                         m, groups_per_face, nchunk, slot_seed, order, offs);
-    }
-    const long long waves = (long long)b * segs * m;
-#define LG(N) hipLaunchKernelGGL((blend_bwd_gather_kernel<N>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, s, \
-                                 m, segs, pitch, seg_off, slots_per_face, nchunk, stage, order, offs, d_table, b)
-    if (c == 64) LG(1); else if (c == 128) LG(2); else if (c == 192) LG(3); else LG(4);
-#undef LG
-    return check_launch(W);
+    stage = (float *)workspace;
+    slot_seed = (int *)(stage + slots * c);
+    order = slot_seed + slots;
+    offs = order + (size_t)b * segs * nchunk * SI_GROUPS * BL_SLOTS;
   }
-#define L(N)                                                                                       \
-  do {                                                                                             \
-    if (bnb)                                                                                       \
-      hipLaunchKernelGGL((blend_bwd_rows_kernel<N, true, false>), grid, dim3(256), 0, s,           \
-                         m, n, segs, seg_len, pitch, seg_off, dy, idx, weight, rel, d_table, d_wx, \
-                         b, nruns, bnz, bnb, (float *)nullptr, (int *)nullptr);                    \
-    else                                                                                           \
-      hipLaunchKernelGGL((blend_bwd_rows_kernel<N, false, false>), grid, dim3(256), 0, s,          \
-                         m, n, segs, seg_len, pitch, seg_off, dy, idx, weight, rel, d_table, d_wx, \
-                         b, nruns, bnz, bnb, (float *)nullptr, (int *)nullptr);                    \
-  } while (0)
-  if (c == 64) L(1); else if (c == 128) L(2); else if (c == 192) L(3); else L(4);
-#undef L
+  const bool built = with_int<1, 2, 3, 4>(c / 64, [&](auto CPT) {
+    with_bool(bnb != nullptr, [&](auto BNB) {
+      with_bool(workspace != nullptr, [&](auto STAGED) {
+        hipLaunchKernelGGL((blend_bwd_rows_kernel<CPT(), BNB(), STAGED()>), grid, dim3(256), 0, s, m, n, segs,
+                           seg_len, pitch, seg_off, dy, idx, weight, rel, d_table, d_wx, b, nruns, bnz, bnb, stage,
+                           slot_seed);
+      });
+    });
+    if (!workspace) return;
+    launch_lds<blend_slot_index_kernel, ((size_t)SI_WAVES * SI_MAX_BINS + SI_WAVES) * sizeof(int)>(
+        dim3((unsigned)(b * segs * nchunk)), dim3(SI_BLOCK), ((size_t)SI_WAVES * m + SI_WAVES) * sizeof(int), s, m,
+        groups_per_face, nchunk, slot_seed, order, offs);
+    const long long waves = (long long)b * segs * m;
+    hipLaunchKernelGGL((blend_bwd_gather_kernel<CPT()>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, s, m, segs,
+                       pitch, seg_off, slots_per_face, nchunk, stage, order, offs, d_table, b);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 

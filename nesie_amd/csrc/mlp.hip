@@ -335,19 +335,10 @@ static int conv_wgrad_impl(const char *W, int b, int cout, int cin, long long p,
   const int runs = wgrad_runs(b, cout, cin, p, &run);
   float *partial = (float *)workspace;
   const dim3 grid(runs, b);
-#define L(WM, WN, MB, NB)                                                                        \
-  do {                                                                                           \
-    const size_t lds = (size_t)(WM * MB + WN * NB) * 32 * WG_P * sizeof(float);                  \
-    auto kern = conv_wgrad_kernel<WM, WN, MB, NB>;                                               \
-    static bool attr = false;                                                                    \
-    if (!attr && lds > 65536) {                                                                  \
-      (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds);                                                       \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, cout, cin, p, x_bstride, dy_bstride, run,  \
-                       vec_ok, dy, x, x_coef, x_relu, partial, bnz, bnb);                        \
-  } while (0)
+#define L(WM, WN, MB, NB)                                                                                     \
+  launch_lds<conv_wgrad_kernel<WM, WN, MB, NB>>(grid, dim3(256), (size_t)(WM * MB + WN * NB) * 32 * WG_P * sizeof(float), \
+                                                s, cout, cin, p, x_bstride, dy_bstride, run, vec_ok, dy, x,  \
+                                                x_coef, x_relu, partial, bnz, bnb)
   // (Cout/32) x (Cin/32) output blocks over 4 waves
   if (mb32 <= 2 && nb32 <= 2) L(2, 2, 1, 1);
   else if (mb32 <= 2 && nb32 <= 4) L(2, 2, 1, 2);

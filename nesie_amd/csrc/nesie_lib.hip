@@ -30,6 +30,17 @@ static const int g_rev_mb = [] { const char *e = getenv("NESIE_PW_REV_MB"); retu
 int walk_dir(long long operand_bytes) {
   return g_rev_mb > 0 && operand_bytes >= (long long)g_rev_mb * 1000000 ? 1 : 0;
 }
+
+// zero-fill as a kernel: a hipMemsetAsync captured into a hipGraph next to the kernel that adds
+// into the same buffer replayed WITHOUT the ordering between the two on this stack (counts came
+// back partly zeroed on later replays), so the clear of such a buffer is an ordinary launch
+__global__ __launch_bounds__(256) void zero_i32_kernel(int n, int *__restrict__ p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+void zero_i32(int *p, int n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, n, p);
+}
 }  // namespace nesie
 
 extern "C" int nesie_abi_version(void) { return 2; }

@@ -356,14 +356,10 @@ extern "C" int nesie_assign_score_withk_forward(int b, int n0, int n1, int k, in
   const int ochunks = cdiv(o, per);
   const long long grid = (long long)b * n1 * ochunks;   // <= elements of the output
   NESIE_REQUIRE(grid < (1ll << 31), W);
-  if (vec)
-    hipLaunchKernelGGL(paconv_fwd_kernel<4>, dim3((unsigned)grid), dim3(PA_BLOCK), 0,
-                       (hipStream_t)stream, n0, n1, k, m, o, ochunks, points, centers, scores, knn_idx,
-                       output);
-  else
-    hipLaunchKernelGGL(paconv_fwd_kernel<1>, dim3((unsigned)grid), dim3(PA_BLOCK), 0,
-                       (hipStream_t)stream, n0, n1, k, m, o, ochunks, points, centers, scores, knn_idx,
-                       output);
+  with_int<4, 1>(vec ? 4 : 1, [&](auto V) {
+    hipLaunchKernelGGL(paconv_fwd_kernel<V()>, dim3((unsigned)grid), dim3(PA_BLOCK), 0, (hipStream_t)stream, n0,
+                       n1, k, m, o, ochunks, points, centers, scores, knn_idx, output);
+  });
   return check_launch(W);
 }
 
@@ -431,21 +427,22 @@ extern "C" int nesie_assign_score_withk_backward(int b, int n0, int n1, int k, i
   const int chunks = cdiv(total, PA_BLOCK * PA_SR);
   const long long sgrid = (long long)b * n0 * chunks;   // <= elements of grad_points
   NESIE_REQUIRE(sgrid < (1ll << 31) && n0 < (1ll << 31) - 1, W);
-#define PA_SCATTER(V, CENTER, ENTRIES, ORDER, SRC, GRAD)                                             \
-  hipLaunchKernelGGL((paconv_scatter_kernel<V, CENTER>), dim3((unsigned)sgrid), dim3(PA_BLOCK), 0, s, \
-                     n0, k, m, o, ENTRIES, pairs, chunks, scores, gT, idx32, ORDER, SRC, GRAD)
+  // grad[i] of a point (a centre: CENTER) from the `entries` pairs a scene has, through their inverted index
+  auto scatter = [&](auto CENTER, int entries, const int *order, const int *src, float *grad) {
+    with_int<4, 1>(vec ? 4 : 1, [&](auto V) {
+      hipLaunchKernelGGL((paconv_scatter_kernel<V(), CENTER()>), dim3((unsigned)sgrid), dim3(PA_BLOCK), 0, s, n0, k,
+                         m, o, entries, pairs, chunks, scores, gT, idx32, order, src, grad);
+    });
+  };
   if (grad_points) {
     if ((st = nesie_inverted_index(b, n0 + 1, pairs, idx32, p_order, p_src, p_tmp, stream))) return st;
-    if (vec) PA_SCATTER(4, false, pairs, p_order, p_src, grad_points);
-    else PA_SCATTER(1, false, pairs, p_order, p_src, grad_points);
+    scatter(std::false_type(), pairs, p_order, p_src, grad_points);
     NESIE_LAUNCHED(W);
   }
   if (grad_centers) {
     if ((st = nesie_inverted_index(b, n0 + 1, n1, cn32, c_order, c_src, c_tmp, stream))) return st;
-    if (vec) PA_SCATTER(4, true, n1, c_order, c_src, grad_centers);
-    else PA_SCATTER(1, true, n1, c_order, c_src, grad_centers);
+    scatter(std::true_type(), n1, c_order, c_src, grad_centers);
     NESIE_LAUNCHED(W);
   }
-#undef PA_SCATTER
   return NESIE_OK;
 }

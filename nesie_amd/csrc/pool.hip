@@ -133,12 +133,11 @@ extern "C" int nesie_group_max_pool_forward(long long rows, int nsample, const f
   NESIE_REQUIRE(threads / 256 + 1 < (1ll << 31), W);
   dim3 grid((unsigned)cdiv(threads, 256));
   hipStream_t s = (hipStream_t)stream;
-#define L(N) hipLaunchKernelGGL(group_max_fwd_kernel<N>, grid, dim3(256), 0, s, rows, \
-                                (const float4 *)x, out, argmax, nt)
   const int nt = stream_nt(rows * nsample * 4) ? 1 : 0;
-  if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
-  else if (lpr == 8) L(8); else L(16);
-#undef L
+  const bool built = with_int<1, 2, 4, 8, 16>(lpr, [&](auto LPR) {
+    hipLaunchKernelGGL(group_max_fwd_kernel<LPR()>, grid, dim3(256), 0, s, rows, (const float4 *)x, out, argmax, nt);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 
@@ -155,12 +154,11 @@ extern "C" int nesie_group_max_pool_backward(long long rows, int nsample,
   NESIE_REQUIRE(threads / 256 + 1 < (1ll << 31), W);
   dim3 grid((unsigned)cdiv(threads, 256));
   hipStream_t s = (hipStream_t)stream;
-#define L(N) hipLaunchKernelGGL(group_max_bwd_kernel<N>, grid, dim3(256), 0, s, rows, \
-                                grad_out, argmax, (float4 *)grad_x, nt)
   const int nt = stream_nt(rows * nsample * 4) ? 1 : 0;
-  if (lpr == 1) L(1); else if (lpr == 2) L(2); else if (lpr == 4) L(4);
-  else if (lpr == 8) L(8); else L(16);
-#undef L
+  const bool built = with_int<1, 2, 4, 8, 16>(lpr, [&](auto LPR) {
+    hipLaunchKernelGGL(group_max_bwd_kernel<LPR()>, grid, dim3(256), 0, s, rows, grad_out, argmax, (float4 *)grad_x, nt);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 
@@ -189,10 +187,10 @@ int launch_group_bwd_lds(int b, int c, int n, long long e_total, long long gstri
   const int e = (int)e_total;
   const int vec = (e & 3) == 0 && (gstride & 3) == 0 &&
                   (((uintptr_t)grad_out | (uintptr_t)idx) & 15) == 0;
-#define L(N) hipLaunchKernelGGL(group_bwd_lds_kernel<N>, grid, dim3(256), lds, s, c, n, e, gstride, vec, \
-                                grad_out, idx, grad_points)
-  if (ch == 8) L(8); else if (ch == 4) L(4); else if (ch == 2) L(2); else L(1);
-#undef L
+  with_int<1, 2, 4, 8>(ch, [&](auto CH) {
+    hipLaunchKernelGGL(group_bwd_lds_kernel<CH()>, grid, dim3(256), lds, s, c, n, e, gstride, vec, grad_out, idx,
+                       grad_points);
+  });
   return check_launch("group_points_backward");
 }
 }  // namespace nesie

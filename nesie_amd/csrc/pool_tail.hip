@@ -446,16 +446,12 @@ extern "C" int nesie_pool_tail_wgrad(int nb, int k, int c, long long p, int ns, 
   const int nwg = pt_gram_groups(nb, p);
   const int shift = pt_ns_shift(ns);
   const size_t lds = (size_t)2 * k * 68 * sizeof(float);
-#define GRAM(K16, C)                                                                                     \
-  hipLaunchKernelGGL((pt_gram_kernel<K16, C>), dim3(nwg), dim3(512), lds, s, nb, p, z_prev, z_bstride,   \
-                     coef_prev, (const float2 *)ent, shift, (int)(p / ns), part_m, part_s, part_w, nwg)
-  if (k == 64 && c == 128) {
-    GRAM(4, 128);
-  } else {
+  if (k != 64 || c != 128) {   // (the one build: pt_gram_kernel<k / 16, c>)
     set_error("%s: no build for %d x %d", W, c, k);
     return NESIE_ERR_UNSUPPORTED;
   }
-#undef GRAM
+  hipLaunchKernelGGL((pt_gram_kernel<4, 128>), dim3(nwg), dim3(512), lds, s, nb, p, z_prev, z_bstride, coef_prev,
+                     (const float2 *)ent, shift, (int)(p / ns), part_m, part_s, part_w, nwg);
   hipLaunchKernelGGL(pt_reduce_ms_kernel, dim3(cdiv(k * k + k, 64)), dim3(1024), 0, s, k, nwg, part_m, part_s, ms);
   hipLaunchKernelGGL(pt_dw_kernel, dim3(c), dim3(1024), 0, s, c, k, nwg, part_w, (const double *)ms,
                      (const float4 *)ab, w, dw);

@@ -102,14 +102,6 @@ __global__ __launch_bounds__(NMS_BLOCK) void aligned_nms_kernel(
   }
 }
 
-// zero-fill as a kernel: a hipMemsetAsync captured into a hipGraph next to the kernel that adds
-// into the same buffer replayed WITHOUT the ordering between the two on this stack (counts came
-// back partly zeroed on later replays), so the clears below are ordinary launches
-__global__ __launch_bounds__(256) void zero_i32_kernel(int n, int *__restrict__ p) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 // ---- points_in_boxes_count ------------------------------------------------------------
 // The inside-test of points_in_boxes.hip (pib_test.h; points_in_boxes_cuda.cu:24-49), LiDAR-frame
 // boxes; counts[b, t] = number of the scene's points inside box t.
@@ -175,7 +167,7 @@ extern "C" int nesie_aligned_3d_nms(int b, int k, const float *boxes, const floa
     return NESIE_ERR_UNSUPPORTED;
   }
   if (k == 0) {
-    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(b, 256)), dim3(256), 0, (hipStream_t)stream, b, count);
+    zero_i32(count, b, (hipStream_t)stream);
     return check_launch(W);
   }
   NESIE_REQUIRE(boxes && scores && classes && picks, W);
@@ -191,8 +183,7 @@ extern "C" int nesie_points_in_boxes_count(int b, int boxes_num, int pts_num,
   NESIE_REQUIRE(b >= 0 && boxes_num >= 0 && pts_num >= 0, W);
   if (b == 0 || boxes_num == 0) return NESIE_OK;
   NESIE_REQUIRE(counts, W);
-  hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv((long long)b * boxes_num, 256)), dim3(256), 0,
-                     (hipStream_t)stream, b * boxes_num, counts);
+  zero_i32(counts, b * boxes_num, (hipStream_t)stream);   // (the count kernel adds into it)
   if (pts_num == 0) return NESIE_OK;
   NESIE_REQUIRE(boxes && pts && b <= 65535, W);
   hipLaunchKernelGGL(points_in_boxes_count_kernel, dim3(cdiv(pts_num, PIC_BLOCK), b),

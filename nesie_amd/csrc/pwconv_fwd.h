@@ -953,13 +953,7 @@ static int pw_launch_epi(const PwFwd &a, int epi, int pg, int grid, size_t lds, 
 // the one prologue / epilogue combination of an input gradient with built operand rows
 template <int KT16, int KH, int WR, int WC, int RW, int EPI>
 static int pw_launch_sparse(const PwFwd &a, int grid, size_t lds, hipStream_t s) {
-  auto kern = pw_fwd_kernel<KT16, KH, WR, WC, RW, EPI, 16, false>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WR * WC * 64), lds, s, a);
+  launch_lds<pw_fwd_kernel<KT16, KH, WR, WC, RW, EPI, 16, false>>(dim3(grid), dim3(WR * WC * 64), lds, s, a);
   return NESIE_OK;
 }
 

@@ -730,18 +730,6 @@ constexpr size_t pw_wgrad_lds(int co16, int ci16, bool fdg = false) {
   return (size_t)2 * ((co16 + ci16) * 16 * 36 + (fdg ? 4 * 36 : 0)) * sizeof(float);
 }
 
-// Launch a 512-thread kernel whose dynamic LDS exceeds the default limit: the limit is raised at the
-// first launch of each kernel instantiation (the flag belongs to this template's instantiation).
-template <auto Kern, typename... Args>
-static void launch_lds(dim3 grid, size_t lds, hipStream_t s, Args... args) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  hipLaunchKernelGGL(Kern, grid, dim3(512), lds, s, args...);
-}
-
 // leave a launch's reduction to nesie_pw_wgrad_flush_deferred (a full table is flushed first)
 static int rd_defer(const RDesc &d, hipStream_t s) {
   if (g_pending.n == RD_MAX) { const int st = rd_flush(s); if (st) return st; }
@@ -782,14 +770,14 @@ static int pw_wgrad_launch(const char *W, const PwWgrad &d, hipStream_t s) {
   dim3 grid;
   const float *xc = nullptr, *cc = nullptr;
   auto launch_sparse = [&](int tiled) {
-    launch_lds<pw_wgrad_sparse_kernel>(dim3(nwg * ng), (size_t)2 * 256 * 36 * sizeof(float) + 256 * sizeof(float2), s, nb,
-                                       ng, p, d.x, d.x_bs, d.x_coef, (const float2 *)d.sp_ent, d.sp_ns == 16 ? 4 : 6,
-                                       (int)(p / d.sp_ns), partial, nwg, rev, tiled);
+    launch_lds<pw_wgrad_sparse_kernel>(dim3(nwg * ng), dim3(512), (size_t)2 * 256 * 36 * sizeof(float) + 256 * sizeof(float2),
+                                       s, nb, ng, p, d.x, d.x_bs, d.x_coef, (const float2 *)d.sp_ent,
+                                       d.sp_ns == 16 ? 4 : 6, (int)(p / d.sp_ns), partial, nwg, rev, tiled);
   };
 #define LKL(LDS, ...)                                                                                                  \
-  launch_lds<pw_wgrad_kernel<__VA_ARGS__>>(grid, LDS, s, nb, ng, co, cw, p, d.dy, d.dy_bs, xc, d.x_bs, cc, ci, lo,     \
-                                           partial, nwg, d.bnz, d.bnb, d.dz, d.d_rb, d.rb_group, rev, d.k4_w, d.fdg_w, \
-                                           d.fdg_part, d.fdg_gpart)
+  launch_lds<pw_wgrad_kernel<__VA_ARGS__>>(grid, dim3(512), LDS, s, nb, ng, co, cw, p, d.dy, d.dy_bs, xc, d.x_bs, cc, \
+                                           ci, lo, partial, nwg, d.bnz, d.bnb, d.dz, d.d_rb, d.rb_group, rev, d.k4_w, \
+                                           d.fdg_w, d.fdg_part, d.fdg_gpart)
 #define LK(CO16, CI16, ...) LKL(pw_wgrad_lds(CO16, CI16), CO16, CI16, __VA_ARGS__)
   if (tiled_mode) {
     nwg = pw_wgrad_tiled_nwg(nb, ng, co, ci, p);

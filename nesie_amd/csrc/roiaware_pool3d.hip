@@ -298,12 +298,11 @@ extern "C" int nesie_roiaware_pool3d_forward(int boxes_num, int pts_num, int cha
   if (e != NESIE_OK) return e;
   const long long want = (nvox + RAP_BLOCK / 64 - 1) / (RAP_BLOCK / 64);
   const int grid = (int)(want < 16384 ? want : 16384);
-  if (pool_method == 0)
-    hipLaunchKernelGGL(rap_pool_kernel<0>, dim3(grid), dim3(RAP_BLOCK), 0, s, nvox, channels, m,
-                       pts_feature, pts_idx_of_voxels, pooled_features, argmax);
-  else
-    hipLaunchKernelGGL(rap_pool_kernel<1>, dim3(grid), dim3(RAP_BLOCK), 0, s, nvox, channels, m,
-                       pts_feature, pts_idx_of_voxels, pooled_features, argmax);
+  const bool built = with_int<0, 1>(pool_method, [&](auto MODE) {
+    hipLaunchKernelGGL(rap_pool_kernel<MODE()>, dim3(grid), dim3(RAP_BLOCK), 0, s, nvox, channels, m, pts_feature,
+                       pts_idx_of_voxels, pooled_features, argmax);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 
@@ -327,11 +326,10 @@ extern "C" int nesie_roiaware_pool3d_backward(int boxes_num, int pts_num, int ou
   const dim3 grid(cdiv(pts_num, RAP_BWD_PT), tiles);
   const size_t lds = (size_t)RAP_BWD_PT * ct * sizeof(float);
   const int V = out_x * out_y * out_z;
-  if (pool_method == 0)
-    hipLaunchKernelGGL(rap_backward_kernel<0>, grid, dim3(64), lds, s, boxes_num, pts_num, V,
-                       channels, m, ct, pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in);
-  else
-    hipLaunchKernelGGL(rap_backward_kernel<1>, grid, dim3(64), lds, s, boxes_num, pts_num, V,
-                       channels, m, ct, pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in);
+  const bool built = with_int<0, 1>(pool_method, [&](auto MODE) {
+    hipLaunchKernelGGL(rap_backward_kernel<MODE()>, grid, dim3(64), lds, s, boxes_num, pts_num, V, channels, m, ct,
+                       pts_idx_of_voxels, argmax, pts_voxel, grad_out, grad_in);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }

@@ -547,7 +547,8 @@ extern "C" int nesie_spconv_out_sites(long long n, const int *indices, int batch
   void *sort_ws = bad + n;
   const long long nk = n * g.kvol;
   const unsigned n_grid = (unsigned)cdiv_ll(n, SC_BLOCK), nk_grid = (unsigned)cdiv_ll(nk, SC_BLOCK);
-  if (hipMemsetAsync(counts, 0, 2 * sizeof(int), s) != hipSuccess) return check_launch(W);
+  zero_i32(counts, 2, s);   // (sc_mark_kernel adds into it)
+  NESIE_LAUNCHED(W);
 
   const IxWorkspace w = ix_carve(sort_ws, n);
   hipLaunchKernelGGL(sc_in_keys_kernel, dim3(n_grid), dim3(SC_BLOCK), 0, s, n, g, indices, w.ka,
@@ -597,7 +598,7 @@ extern "C" int nesie_spconv_gather_table(long long m, const int *out_indices, lo
   NESIE_REQUIRE(out_indices && nbr && pair_num, W);
   NESIE_REQUIRE(n == 0 || (sorted_keys && sorted_rows), W);
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(pair_num, 0, g.kvol * sizeof(int), s) != hipSuccess) return check_launch(W);
+  zero_i32(pair_num, g.kvol, s);   // (sc_table_kernel adds into it)
   const long long total = m * g.kvol;
   hipLaunchKernelGGL(sc_table_kernel, dim3((unsigned)cdiv_ll(total, SC_BLOCK)), dim3(SC_BLOCK), 0,
                      s, total, n, g, subm, out_indices, sorted_keys, sorted_rows, nbr, pair_num);

@@ -437,15 +437,11 @@ extern "C" int nesie_dynamic_scatter_forward(long long n, int c, const float *fe
                      order, w.flag, coors, coors_map, voxel_coors, voxel_start, w.meta);
   NESIE_LAUNCHED(W);
   const dim3 grid(vx_wave_grid(n)), block(VX_BLOCK);
-  if (reduce_type == 0)
-    hipLaunchKernelGGL(vx_reduce_kernel<0>, grid, block, 0, s, c, feats, order, voxel_start,
-                       num_voxels, w.meta, voxel_feats, reduce_count);
-  else if (reduce_type == 1)
-    hipLaunchKernelGGL(vx_reduce_kernel<1>, grid, block, 0, s, c, feats, order, voxel_start,
-                       num_voxels, w.meta, voxel_feats, reduce_count);
-  else
-    hipLaunchKernelGGL(vx_reduce_kernel<2>, grid, block, 0, s, c, feats, order, voxel_start,
-                       num_voxels, w.meta, voxel_feats, reduce_count);
+  const bool built = with_int<0, 1, 2>(reduce_type, [&](auto RT) {
+    hipLaunchKernelGGL(vx_reduce_kernel<RT()>, grid, block, 0, s, c, feats, order, voxel_start, num_voxels, w.meta,
+                       voxel_feats, reduce_count);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
 
@@ -478,11 +474,10 @@ extern "C" int nesie_dynamic_scatter_backward(long long n, int c, const float *g
     set_error("%s: %lld x %d elements are more than one launch covers", W, n, c);
     return NESIE_ERR_UNSUPPORTED;
   }
-  if (reduce_type == 0)
-    hipLaunchKernelGGL(vx_backward_add_kernel<0>, dim3((unsigned)blocks), block, 0, s, total, c,
-                       grad_voxel, coors_map, reduce_count, grad_feats);
-  else
-    hipLaunchKernelGGL(vx_backward_add_kernel<1>, dim3((unsigned)blocks), block, 0, s, total, c,
-                       grad_voxel, coors_map, reduce_count, grad_feats);
+  const bool built = with_int<0, 1>(reduce_type, [&](auto RT) {   // (2 has left above)
+    hipLaunchKernelGGL(vx_backward_add_kernel<RT()>, dim3((unsigned)blocks), block, 0, s, total, c, grad_voxel,
+                       coors_map, reduce_count, grad_feats);
+  });
+  NESIE_REQUIRE(built, W);
   return check_launch(W);
 }
