@@ -542,6 +542,46 @@ int nesie_bn_relu_backward_apply(int b, int c, long long p, const float *dy, con
                                  float *dx, float *dgamma, float *dbeta, int group,
                                  float *d_row_bias, void *stream);
 
+/* Synchronised training BatchNorm (+ ReLU): the norm above cut open between each local reduction
+ * and its finalise step, so that the caller can put a SUM all-reduce in the cut (reference:
+ * NaiveSyncBatchNorm1d/2d, mmdet3d/ops/norm.py:27-133).  x, y, dy, dx [B, C, P] fp32 of ONE rank.
+ *   local_moments : moments [C][3] float64 = (n_local, sum x, sum x^2): raw moments, the one form
+ *                   that adds across ranks (the fp32 partials are taken about a per-rank shift and
+ *                   un-shifted in double).  The caller all-reduces `moments`.
+ *   forward_apply : from the reduced moments, in double: mean = sum x / n, var = max(sum x^2 / n -
+ *                   mean^2, 0), invstd = 1 / sqrt(var + eps); writes fwd_coef [C,4] = (scale, bias,
+ *                   mean, invstd), y = relu?(x * scale + bias), and updates running_mean /
+ *                   running_var (both NULL = skip) with the BIASED variance, as the reference does.
+ *                   The statistics are those of the concatenated batch whatever the ranks' sizes
+ *                   (n travels in the moments).
+ *   backward_local: sums [C][2] float64 = (sum g, sum g * xhat) over this rank's positions, g = dy
+ *                   masked by x * scale + bias > 0 when relu (the forward's two fp32 operations,
+ *                   scale / bias from fwd_coef); dgamma, dbeta [C] fp32 (NULL = skip) are these
+ *                   LOCAL sums.  The caller all-reduces `sums`.
+ *   backward_apply: dx = gamma * invstd * (g - sum g / n - xhat * sum g xhat / n) from the reduced
+ *                   sums and the reduced moments; the same mask expression.
+ *                   Both backward passes take mean and invstd in double from the reduced moments
+ *                   and `eps` (the forward's) and evaluate xhat and the closed form in double,
+ *                   rounding dx once: with few positions per channel the form cancels completely.
+ * Fixed summation order, no atomics, no host read of a device value.  b, c, p >= 1.  workspace:
+ * nesie_syncbn_workspace_bytes(b, c, p) for the two local passes; tensors 16-byte aligned when
+ * p % 4 == 0. */
+size_t nesie_syncbn_workspace_bytes(int b, int c, long long p);
+int nesie_syncbn_local_moments(int b, int c, long long p, const float *x, double *moments,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int nesie_syncbn_forward_apply(int b, int c, long long p, const float *x, const double *moments,
+                               const float *gamma, const float *beta, float *running_mean,
+                               float *running_var, float momentum, float eps, int relu, float *y,
+                               float *fwd_coef, void *stream);
+int nesie_syncbn_backward_local(int b, int c, long long p, const float *dy, const float *x,
+                                const float *fwd_coef, const double *moments, float eps, int relu,
+                                double *sums, float *dgamma, float *dbeta, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int nesie_syncbn_backward_apply(int b, int c, long long p, const float *dy, const float *x,
+                                const float *fwd_coef, const float *gamma, const double *sums,
+                                const double *moments, float eps, int relu, float *dx,
+                                void *stream);
+
 /* Training BatchNorm + ReLU + max over the neighbourhood axis for the LAST layer of a
  * set-abstraction MLP: x[B, C, M, ns] -> pooled[B, C, M] (+ argmax[B, C, M], one byte, smallest
  * index on ties) without writing the normalised tensor.  Reference: ConvModule's BN2d + ReLU

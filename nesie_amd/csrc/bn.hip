@@ -13,6 +13,10 @@
 // pair costs 5 and 10): the reduce rebuilds xhat from y where y > 0 (the only places the
 // sums need it), the apply re-derives the mask from x with the forward's own scale/bias.  Sums are taken about a per-channel shift (the channel's first
 // element) so E[x^2]-E[x]^2 does not cancel; partials are combined in double.
+//
+// The synchronised norm (nesie_syncbn_*: NaiveSyncBatchNorm1d/2d, reference mmdet3d/ops/norm.py:27-133)
+// is the same pipeline cut open between each local reduction and its finalise step, with float64
+// moments / sums leaving the rank for the caller's all-reduce: same pass counts.
 #include "common.h"
 #include <stdlib.h>
 
@@ -129,10 +133,78 @@ __global__ void bn_finalize_kernel(BnFwdFin f, int c_total) {
   if ((int)blockIdx.x < c_total) bn_fwd_finalize(f, blockIdx.x, true, sh);
 }
 
-template <bool RELU, bool NT>
+// ---- synchronised norm: the pipeline cut open between the local reduction and the finalise ----
+// A rank's shifted fp32 partials cannot be added to another rank's (each has its own shift), so
+// they leave the rank as RAW moments in double, moments[c*3 + {0,1,2}] = n, sum(x), sum(x^2):
+// the one form a plain SUM all-reduce combines.  One wave per channel folds the partials 64 at a
+// time in double (fixed order) and un-shifts them, all in double.
+__global__ __launch_bounds__(64) void syncbn_moments_kernel(
+    int nslice, double n, const float *__restrict__ x, long long p,
+    const float *__restrict__ partial, double *__restrict__ moments) {
+  const int c = blockIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < nslice; i += 64) {
+    s0 += (double)partial[((size_t)c * nslice + i) * 2];
+    s1 += (double)partial[((size_t)c * nslice + i) * 2 + 1];
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (threadIdx.x == 0) {
+    const double shift = (double)x[(size_t)c * p];      // bn_stats_kernel's shift
+    moments[c * 3 + 0] = n;
+    moments[c * 3 + 1] = s0 + n * shift;
+    moments[c * 3 + 2] = s1 + 2.0 * shift * s0 + n * shift * shift;
+  }
+}
+
+// the statistics -> coefficients step from the all-reduced moments (n is the GLOBAL count and
+// travels in them: no host read).  running_var takes the BIASED variance, as the reference's
+// NaiveSyncBatchNorm does (mmdet3d/ops/norm.py:68-71).
+struct SyncFwdFin {
+  const double *moments; const float *gamma; const float *beta; float *running_mean;
+  float *running_var; float momentum; float eps; float *coef;
+};
+
+// mean, biased variance and invstd of channel c in double.  Every pass of the synchronised norm
+// derives them from the reduced moments with this one expression, so all of them see the same bits.
+struct SyncStats { double n, mean, var, invstd; };
+__device__ __forceinline__ SyncStats syncbn_stats(const double *moments, int c, float eps) {
+  SyncStats s;
+  s.n = moments[c * 3];
+  s.mean = moments[c * 3 + 1] / s.n;
+  s.var = moments[c * 3 + 2] / s.n - s.mean * s.mean;
+  if (s.var < 0.0) s.var = 0.0;
+  s.invstd = 1.0 / sqrt(s.var + (double)eps);
+  return s;
+}
+
+__device__ __forceinline__ void bn_fwd_finalize(const SyncFwdFin &f, int c, bool writer, float *sh) {
+  if (threadIdx.x == 0) {
+    const SyncStats st = syncbn_stats(f.moments, c, f.eps);
+    const double mean = st.mean, var = st.var, invstd = st.invstd;
+    const double g = f.gamma ? (double)f.gamma[c] : 1.0, bt = f.beta ? (double)f.beta[c] : 0.0;
+    sh[0] = (float)(g * invstd);
+    sh[1] = (float)(bt - mean * g * invstd);
+    if (writer) {
+      if (f.running_mean) {
+        f.running_mean[c] = (float)((1.0 - f.momentum) * f.running_mean[c] + f.momentum * mean);
+        f.running_var[c] = (float)((1.0 - f.momentum) * f.running_var[c] + f.momentum * var);
+      }
+      f.coef[c * 4 + 0] = sh[0];
+      f.coef[c * 4 + 1] = sh[1];
+      f.coef[c * 4 + 2] = (float)mean;
+      f.coef[c * 4 + 3] = (float)invstd;
+    }
+  }
+  __syncthreads();
+}
+
+// Fin: where scale / bias come from -- BnFwdFin (this rank's shifted partials) or SyncFwdFin (the
+// all-reduced raw moments of the synchronised norm, below); bn_fwd_finalize is overloaded on it
+template <bool RELU, bool NT, typename Fin = BnFwdFin>
 __global__ __launch_bounds__(BN_BLOCK) void bn_apply_kernel(
     int c_total, long long p, const float *__restrict__ x, const float *__restrict__ row_bias,
-    int group, BnFwdFin fin, float *__restrict__ y) {
+    int group, Fin fin, float *__restrict__ y) {
   __shared__ float shc[2];
   const int c = blockIdx.y, b = blockIdx.z;
   bn_fwd_finalize(fin, c, blockIdx.x == 0 && b == 0, shc);
@@ -294,6 +366,124 @@ __global__ void bn_bwd_finalize_kernel(BnBwdFin f, int c_total, float *coef) {
   if (c >= c_total) return;
   bn_bwd_finalize(f, c, true, sh);
   if (threadIdx.x == 0) { coef[c * 4 + 0] = sh[0]; coef[c * 4 + 1] = sh[1]; coef[c * 4 + 2] = sh[2]; }
+}
+
+// ---- synchronised norm, backward ------------------------------------------------------------
+// Both passes work in DOUBLE on the fp32 tensors, with mean / invstd from syncbn_stats: the vector
+// unit runs fp64 at the unpacked fp32 rate and the passes are HBM-bound, and the closed form
+// g - sum(g)/n - xhat * sum(g xhat)/n cancels completely when a channel has few positions (n = 2:
+// xhat = +-1, what is left is O(eps / var)) -- in fp32 the rounding of xhat alone is larger than
+// the result.  The ReLU mask stays the fp32 expression x * scale + bias > 0 of bn_apply_kernel
+// (y is not kept), identical in both passes.
+//
+// The local pass: partial[(c * nslice + b * sp + s) * 2 + {0,1}] = sum(g), sum(g * xhat) over one
+// span, double.  Reads dy and x once.
+template <bool RELU>
+__global__ __launch_bounds__(BN_BLOCK) void syncbn_bwd_reduce_kernel(
+    int c_total, long long p, int sp, const float *__restrict__ dy, const float *__restrict__ x,
+    const float *__restrict__ fwd_coef, const double *__restrict__ moments, float eps,
+    double *__restrict__ partial) {
+  __shared__ double sh[BN_BLOCK / 64];
+  const int s = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+  const size_t base = ((size_t)b * c_total + c) * p;
+  const float sc = fwd_coef[c * 4 + 0], bi = fwd_coef[c * 4 + 1];
+  const SyncStats st = syncbn_stats(moments, c, eps);
+  const long long lo = (long long)s * BN_SPAN;
+  const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
+  double a0 = 0.0, a1 = 0.0;   // sum(g), sum(g * (x - mean)); invstd is applied once at the end
+  if ((p & 3) == 0) {
+    for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
+      float4 g = *(const float4 *)(dy + base + i);      // both read again by the apply pass
+      const float4 v = *(const float4 *)(x + base + i);
+      if (RELU) {
+        g.x = v.x * sc + bi > 0.f ? g.x : 0.f; g.y = v.y * sc + bi > 0.f ? g.y : 0.f;
+        g.z = v.z * sc + bi > 0.f ? g.z : 0.f; g.w = v.w * sc + bi > 0.f ? g.w : 0.f;
+      }
+      a0 += ((double)g.x + (double)g.y) + ((double)g.z + (double)g.w);
+      a1 = fma((double)g.x, (double)v.x - st.mean, a1);
+      a1 = fma((double)g.y, (double)v.y - st.mean, a1);
+      a1 = fma((double)g.z, (double)v.z - st.mean, a1);
+      a1 = fma((double)g.w, (double)v.w - st.mean, a1);
+    }
+  } else {
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
+      float g = dy[base + i];
+      const float v = x[base + i];
+      if (RELU) g = v * sc + bi > 0.f ? g : 0.f;
+      a0 += (double)g;
+      a1 = fma((double)g, (double)v - st.mean, a1);
+    }
+  }
+  a0 = block_sum<BN_BLOCK>(a0, sh);
+  a1 = block_sum<BN_BLOCK>(a1, sh);
+  if (threadIdx.x == 0) {
+    const size_t o = ((size_t)c * (gridDim.z * sp) + (size_t)b * sp + s) * 2;
+    partial[o] = a0; partial[o + 1] = a1 * st.invstd;
+  }
+}
+
+// one wave per channel: the spans' partials added 64 at a time (fixed order) -> sums[c*2 + {0,1}]
+// for the all-reduce, and this rank's own parameter gradients (the flat-gradient all-reduce
+// averages those afterwards)
+__global__ __launch_bounds__(64) void syncbn_bwd_fold_kernel(
+    int nslice, const double *__restrict__ partial, double *__restrict__ sums,
+    float *__restrict__ dgamma, float *__restrict__ dbeta) {
+  const int c = blockIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < nslice; i += 64) {
+    s0 += partial[((size_t)c * nslice + i) * 2];
+    s1 += partial[((size_t)c * nslice + i) * 2 + 1];
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (threadIdx.x == 0) {
+    sums[c * 2 + 0] = s0; sums[c * 2 + 1] = s1;
+    if (dbeta) dbeta[c] = (float)s0;
+    if (dgamma) dgamma[c] = (float)s1;
+  }
+}
+
+// dx = a (g - k1 - xhat k2), a = gamma invstd, k1 = sum(g) / n, k2 = sum(g xhat) / n from the
+// all-reduced sums and the global n, evaluated as fma(-(x - mean), a invstd k2, fma(a, g, -a k1))
+// in double and rounded once.  Reads dy and x, writes dx.
+template <bool RELU, bool NT>
+__global__ __launch_bounds__(BN_BLOCK) void syncbn_bwd_apply_kernel(
+    int c_total, long long p, const float *__restrict__ dy, const float *__restrict__ x,
+    const float *__restrict__ fwd_coef, const float *__restrict__ gamma,
+    const double *__restrict__ sums, const double *__restrict__ moments, float eps,
+    float *__restrict__ dx) {
+  const int c = blockIdx.y, b = blockIdx.z;
+  const float sc = fwd_coef[c * 4 + 0], bi = fwd_coef[c * 4 + 1];
+  const SyncStats st = syncbn_stats(moments, c, eps);
+  const double a = (gamma ? (double)gamma[c] : 1.0) * st.invstd;
+  const double ak1 = -(a * (sums[c * 2] / st.n)), q = a * st.invstd * (sums[c * 2 + 1] / st.n);
+  const double mean = st.mean;
+  const size_t base = ((size_t)b * c_total + c) * p;
+  const long long lo = (long long)blockIdx.x * BN_SPAN;
+  const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
+  if ((p & 3) == 0) {
+    for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
+      float4 g = ld4<NT>(dy + base + i);
+      const float4 v = ld4<NT>(x + base + i);
+      if (RELU) {
+        g.x = v.x * sc + bi > 0.f ? g.x : 0.f; g.y = v.y * sc + bi > 0.f ? g.y : 0.f;
+        g.z = v.z * sc + bi > 0.f ? g.z : 0.f; g.w = v.w * sc + bi > 0.f ? g.w : 0.f;
+      }
+      float4 r;
+      r.x = (float)fma(mean - (double)v.x, q, fma(a, (double)g.x, ak1));
+      r.y = (float)fma(mean - (double)v.y, q, fma(a, (double)g.y, ak1));
+      r.z = (float)fma(mean - (double)v.z, q, fma(a, (double)g.z, ak1));
+      r.w = (float)fma(mean - (double)v.w, q, fma(a, (double)g.w, ak1));
+      st4<NT>(dx + base + i, r);
+    }
+  } else {
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
+      float g = dy[base + i];
+      const float v = x[base + i];
+      if (RELU) g = v * sc + bi > 0.f ? g : 0.f;
+      dx[base + i] = (float)fma(mean - (double)v, q, fma(a, (double)g, ak1));
+    }
+  }
 }
 
 template <bool RELU, bool NT>
@@ -586,6 +776,106 @@ extern "C" int nesie_bn_relu_backward_apply(int b, int c, long long p, const flo
   with_bool(nt, [&](auto N) {
     hipLaunchKernelGGL((bn_bwd_apply_kernel<true, N()>), grid, dim3(BN_BLOCK), 0, s, c, p, dy, x,
                        fwd_coef, fin, (const float *)nullptr, group, d_row_bias, dx, 1);
+  });
+  return check_launch(W);
+}
+
+// ---- synchronised norm: four entry points, a collective of the caller's between each pair ------
+// scratch of the two local passes: the spans' partials, fp32 forward and double backward
+extern "C" size_t nesie_syncbn_workspace_bytes(int b, int c, long long p) {
+  if (b <= 0 || c <= 0 || p <= 0) return 0;
+  return (size_t)c * ((size_t)b * bn_sp(p)) * 2 * sizeof(double);
+}
+
+// ws_needed: the two passes that leave partials; the apply passes take none
+static int syncbn_check(const char *W, int b, int c, long long p, bool ws_needed, const void *ws,
+                        size_t ws_bytes) {
+  NESIE_REQUIRE(b >= 1 && c >= 1 && p >= 1, W);
+  NESIE_REQUIRE(b <= 65535 && c <= 65535 && bn_sp(p) < (1 << 30), W);
+  NESIE_REQUIRE(!ws_needed || (ws && ws_bytes >= nesie_syncbn_workspace_bytes(b, c, p)), W);
+  return NESIE_OK;
+}
+// the float4 path (p % 4 == 0) needs 16-byte rows; the scalar tail path does not
+static bool syncbn_aligned(long long p, const void *a, const void *b, const void *c) {
+  return (p & 3) != 0 || ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0);
+}
+
+extern "C" int nesie_syncbn_local_moments(int b, int c, long long p, const float *x,
+                                          double *moments, void *workspace,
+                                          size_t workspace_bytes, void *stream) {
+  const char *W = "syncbn_local_moments";
+  int st = syncbn_check(W, b, c, p, true, workspace, workspace_bytes);
+  if (st) return st;
+  NESIE_REQUIRE(x && moments && syncbn_aligned(p, x, nullptr, nullptr), W);
+  hipStream_t s = (hipStream_t)stream;
+  const int sp = bn_sp(p), nslice = b * sp;
+  float *partial = (float *)workspace;
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(sp, c, b), dim3(BN_BLOCK), 0, s, c, p, sp, x,
+                     (const float *)nullptr, 1, partial, 0);
+  hipLaunchKernelGGL(syncbn_moments_kernel, dim3(c), dim3(64), 0, s, nslice,
+                     (double)b * (double)p, x, p, (const float *)partial, moments);
+  return check_launch(W);
+}
+
+extern "C" int nesie_syncbn_forward_apply(int b, int c, long long p, const float *x,
+                                          const double *moments, const float *gamma,
+                                          const float *beta, float *running_mean,
+                                          float *running_var, float momentum, float eps, int relu,
+                                          float *y, float *fwd_coef, void *stream) {
+  const char *W = "syncbn_forward_apply";
+  int st = syncbn_check(W, b, c, p, false, nullptr, 0);
+  if (st) return st;
+  NESIE_REQUIRE(x && y && moments && fwd_coef && syncbn_aligned(p, x, y, nullptr), W);
+  NESIE_REQUIRE((running_mean == nullptr) == (running_var == nullptr), W);
+  const SyncFwdFin fin{moments, gamma, beta, running_mean, running_var, momentum, eps, fwd_coef};
+  const bool nt = bn_use_nt((long long)b * c * p);
+  with_bool(relu, [&](auto R) {
+    with_bool(nt, [&](auto N) {
+      hipLaunchKernelGGL((bn_apply_kernel<R(), N(), SyncFwdFin>), dim3(bn_sp(p), c, b), dim3(BN_BLOCK), 0,
+                         (hipStream_t)stream, c, p, x, (const float *)nullptr, 1, fin, y);
+    });
+  });
+  return check_launch(W);
+}
+
+extern "C" int nesie_syncbn_backward_local(int b, int c, long long p, const float *dy,
+                                           const float *x, const float *fwd_coef,
+                                           const double *moments, float eps, int relu,
+                                           double *sums, float *dgamma, float *dbeta,
+                                           void *workspace, size_t workspace_bytes,
+                                           void *stream) {
+  const char *W = "syncbn_backward_local";
+  int st = syncbn_check(W, b, c, p, true, workspace, workspace_bytes);
+  if (st) return st;
+  NESIE_REQUIRE(dy && x && fwd_coef && moments && sums && syncbn_aligned(p, dy, x, nullptr), W);
+  NESIE_REQUIRE(((uintptr_t)workspace & 7) == 0, W);
+  hipStream_t s = (hipStream_t)stream;
+  const int sp = bn_sp(p), nslice = b * sp;
+  double *partial = (double *)workspace;
+  with_bool(relu, [&](auto R) {
+    hipLaunchKernelGGL(syncbn_bwd_reduce_kernel<R()>, dim3(sp, c, b), dim3(BN_BLOCK), 0, s, c, p, sp, dy, x,
+                       fwd_coef, moments, eps, partial);
+  });
+  hipLaunchKernelGGL(syncbn_bwd_fold_kernel, dim3(c), dim3(64), 0, s, nslice, (const double *)partial,
+                     sums, dgamma, dbeta);
+  return check_launch(W);
+}
+
+extern "C" int nesie_syncbn_backward_apply(int b, int c, long long p, const float *dy,
+                                           const float *x, const float *fwd_coef,
+                                           const float *gamma, const double *sums,
+                                           const double *moments, float eps, int relu, float *dx,
+                                           void *stream) {
+  const char *W = "syncbn_backward_apply";
+  int st = syncbn_check(W, b, c, p, false, nullptr, 0);
+  if (st) return st;
+  NESIE_REQUIRE(dy && x && fwd_coef && sums && moments && dx && syncbn_aligned(p, dy, x, dx), W);
+  const bool nt = bn_use_nt((long long)b * c * p);
+  with_bool(relu, [&](auto R) {
+    with_bool(nt, [&](auto N) {
+      hipLaunchKernelGGL((syncbn_bwd_apply_kernel<R(), N()>), dim3(bn_sp(p), c, b), dim3(BN_BLOCK), 0,
+                         (hipStream_t)stream, c, p, dy, x, fwd_coef, gamma, sums, moments, eps, dx);
+    });
   });
   return check_launch(W);
 }

@@ -143,16 +143,16 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 }
 
 // Sum over a workgroup of BLOCK threads, result in every thread: wave_sum, then the waves' sums
-// in ascending wave order.  sh: BLOCK / 64 floats of LDS; the barrier in front lets a caller hand
-// in the same sh for one sum after another.
-template <int BLOCK>
-__device__ __forceinline__ float block_sum(float v, float *sh) {
+// in ascending wave order.  sh: BLOCK / 64 values (float or double) of LDS; the barrier in front
+// lets a caller hand in the same sh for one sum after another.
+template <int BLOCK, typename T>
+__device__ __forceinline__ T block_sum(T v, T *sh) {
   v = wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) sh[wave] = v;
   __syncthreads();
-  float t = 0.f;
+  T t = 0;
 #pragma unroll
   for (int w = 0; w < BLOCK / 64; ++w) t += sh[w];
   return t;

@@ -2,9 +2,12 @@
 exchange per iteration -- an all-reduce(mean) of the flat gradient vector
 (2 640 477 fp32 = 10.56 MB for Nesie-VoteNet) over RCCL/xGMI.
 
-BatchNorm stays per-rank (the configs use plain BN, not SyncBN) and the EMA teacher is
-a deterministic function of the post-all-reduce parameters, so nothing else crosses
-ranks.  The message is latency-bound (a ring moves ~18.5 MB per GPU per step), so the
+BatchNorm stays per-rank by default (the configs use plain BN, not SyncBN) and the EMA
+teacher is a deterministic function of the post-all-reduce parameters, so nothing else
+crosses ranks.  A model built with ``norm_cfg=dict(type='naiveSyncBN1d' / 'naiveSyncBN2d')``
+takes its batch statistics over every rank instead (``mmdet3d_ops/norm.py``): two more
+all-reduces per such layer per step, 3C float64 forward and 2C backward, issued eagerly --
+that path cannot be captured in a graph.  The message is latency-bound (a ring moves ~18.5 MB per GPU per step), so the
 gradients travel as a single flat bucket rather than per-tensor collectives.
 """
 import os

@@ -1731,6 +1731,63 @@ class HipKernels:
         _launch("nesie_bn_relu_backward", x, b, c, p, dy, x, y, gamma, beta, save_mean, save_invstd,
                 fwd_coef, bool(relu), dx, dgamma, dbeta, row_bias, group, d_row_bias, ws, need)
 
+    # ---- synchronised norm: the caller all-reduces ``moments`` / ``sums`` between each pair ----
+    @staticmethod
+    def _syncbn_dims(x, *same):
+        _check(x, *same); _f32(x, *same)
+        assert x.dim() >= 2 and all(t.shape == x.shape for t in same)
+        b, c = x.shape[:2]
+        return b, c, (x.numel() // (b * c) if b * c else 0)
+
+    @staticmethod
+    def _f64(t, shape):
+        _check(t)
+        if t.dtype != torch.float64 or tuple(t.shape) != shape:
+            raise TypeError(f"expected float64 {shape}, got {t.dtype} {tuple(t.shape)}")
+
+    def syncbn_local_moments(self, x, moments):
+        """moments (C, 3) float64 <- (n_local, sum x, sum x^2) of x (B, C, *) per channel."""
+        b, c, p = self._syncbn_dims(x)
+        self._f64(moments, (c, 3))
+        need = _lib.load().nesie_syncbn_workspace_bytes(b, c, p)
+        ws = _workspace(need, x.device)
+        _launch("nesie_syncbn_local_moments", x, b, c, p, x, moments, ws, need)
+
+    def syncbn_forward_apply(self, x, moments, gamma, beta, running_mean, running_var, momentum,
+                             eps, relu, y, fwd_coef):
+        """y, fwd_coef (C, 4) and the running statistics from the all-reduced ``moments``."""
+        b, c, p = self._syncbn_dims(x, y)
+        self._f64(moments, (c, 3))
+        _check(fwd_coef); _f32(fwd_coef)
+        assert tuple(fwd_coef.shape) == (c, 4)
+        for v in (gamma, beta, running_mean, running_var):
+            if v is not None:
+                _check(v); _f32(v)
+                assert v.numel() == c
+        _launch("nesie_syncbn_forward_apply", x, b, c, p, x, moments, gamma, beta, running_mean,
+                running_var, float(momentum), float(eps), bool(relu), y, fwd_coef)
+
+    def syncbn_backward_local(self, dy, x, fwd_coef, moments, eps, relu, sums, dgamma, dbeta):
+        """sums (C, 2) float64 <- (sum g, sum g * xhat) over this rank; dgamma, dbeta: the same
+        local sums in fp32.  ``moments``: the reduced ones of the forward; ``eps``: its eps."""
+        b, c, p = self._syncbn_dims(x, dy)
+        self._f64(sums, (c, 2)); self._f64(moments, (c, 3))
+        _check(fwd_coef, dgamma, dbeta); _f32(fwd_coef, dgamma, dbeta)
+        assert tuple(fwd_coef.shape) == (c, 4) and dgamma.numel() == c and dbeta.numel() == c
+        need = _lib.load().nesie_syncbn_workspace_bytes(b, c, p)
+        ws = _workspace(need, x.device)
+        _launch("nesie_syncbn_backward_local", x, b, c, p, dy, x, fwd_coef, moments, float(eps),
+                bool(relu), sums, dgamma, dbeta, ws, need)
+
+    def syncbn_backward_apply(self, dy, x, fwd_coef, gamma, sums, moments, eps, relu, dx):
+        """dx from the all-reduced ``sums`` and the reduced ``moments``."""
+        b, c, p = self._syncbn_dims(x, dy, dx)
+        self._f64(sums, (c, 2)); self._f64(moments, (c, 3))
+        _check(fwd_coef); _f32(fwd_coef)
+        assert tuple(fwd_coef.shape) == (c, 4) and (gamma is None or gamma.numel() == c)
+        _launch("nesie_syncbn_backward_apply", x, b, c, p, dy, x, fwd_coef, gamma, sums, moments,
+                float(eps), bool(relu), dx)
+
     def assign_score_withk_forward(self, b, n0, n1, m, k, o, points, centers, scores, knn_idx,
                                    output):
         """output (B, O, N1, K) <- sum_m scores * (points[knn_idx] - centers[knn_idx[..., 0]]),

@@ -1,8 +1,10 @@
 """Host-side mirror of ``mmdet3d.ops`` (reference mmdet3d/ops/__init__.py:1-41).  The reference's
 own operator families are real, and so is the one mmcv re-export that sits on a training path:
 ``sigmoid_focal_loss`` / ``SigmoidFocalLoss`` (``focal_loss.py``, the kernel behind mmdet's
-``FocalLoss``).  The rest of the reference's ``__all__`` (the other mmcv re-exports: nms, RoIAlign,
-NaiveSyncBatchNorm ..., and SparseBottleneck) resolves to stubs that raise on use, so
+``FocalLoss``).  ``NaiveSyncBatchNorm1d`` / ``NaiveSyncBatchNorm2d`` (``norm.py``; the norm types
+``naiveSyncBN1d`` / ``naiveSyncBN2d`` of ``ConvModule``) are real too: batch statistics over every
+rank of a process group, on the ``nesie_syncbn_*`` kernels.  The rest of the reference's ``__all__``
+(the other mmcv re-exports: nms, RoIAlign ..., and SparseBottleneck) resolves to stubs that raise on use, so
 ``from mmdet3d.ops import X`` style code keeps importing ("import-time
 requirement").
 
@@ -34,6 +36,7 @@ from .sparse_block import SparseBasicBlock, make_sparse_convmodule
 from .voxel import DynamicScatter, Voxelization, dynamic_scatter, voxelization
 from .paconv import PAConvCUDA
 from .focal_loss import SigmoidFocalLoss, sigmoid_focal_loss
+from .norm import NaiveSyncBatchNorm1d, NaiveSyncBatchNorm2d
 from .paconv_sa_module import (PAConvCUDASAModule, PAConvCUDASAModuleMSG, PAConvSAModule,
                                PAConvSAModuleMSG)
 
@@ -50,11 +53,11 @@ _HOT = [
     'SparseBasicBlock', 'make_sparse_convmodule',
     'PAConvCUDA', 'PAConvSAModuleMSG', 'PAConvSAModule', 'PAConvCUDASAModule',
     'PAConvCUDASAModuleMSG', 'sigmoid_focal_loss', 'SigmoidFocalLoss',
+    'NaiveSyncBatchNorm1d', 'NaiveSyncBatchNorm2d',
 ]
 _OUT_OF_SCOPE = [
     'nms', 'soft_nms', 'RoIAlign', 'roi_align', 'get_compiler_version',
-    'get_compiling_cuda_version', 'NaiveSyncBatchNorm1d', 'NaiveSyncBatchNorm2d',
-    'batched_nms',
+    'get_compiling_cuda_version', 'batched_nms',
     'SparseBottleneck', 'assign_score_withk', 'PAConv',
 ]
 _IN_SUBPACKAGE = {'assign_score_withk': 'paconv', 'PAConv': 'paconv'}

@@ -257,3 +257,161 @@ class FusedBNReLU2d(_FusedBNReLU, nn.BatchNorm2d):
     def __init__(self, num_features, relu=True, **kw):
         nn.BatchNorm2d.__init__(self, num_features, **kw)
         self._init_fused(relu)
+
+
+# ---- synchronised batch statistics (reference mmdet3d/ops/norm.py:27-133) ----------------------
+def _sync_group_active(group):
+    """A process group is up and either spans several ranks or ``dp.force_process_group()`` asks
+    for the real collectives on one rank."""
+    import torch.distributed as dist
+    from ..dp import force_process_group
+    if not (dist.is_available() and dist.is_initialized()):
+        return False
+    return dist.get_world_size(group) > 1 or force_process_group()
+
+
+def _channel_view(v, x):
+    return v.view(1, -1, *([1] * (x.dim() - 2)))
+
+
+class SyncBNReLUTrain(Function):
+    """Training BatchNorm (+ ReLU) over the batches of ALL ranks of ``group``: local raw moments
+    (C, 3) float64 -> all-reduce(SUM) -> apply; backward: local (sum g, sum g xhat) (C, 2) float64
+    -> all-reduce(SUM) -> apply.  Two collectives per layer per step.  On a ``hip`` tensor the four
+    steps are the ``nesie_syncbn_*`` kernels; on any other tensor (CPU ranks under gloo, an
+    injected back end) the same mathematics in torch ops.  x and fwd_coef are saved, y is not.
+    dgamma / dbeta are the LOCAL sums: the flat-gradient all-reduce averages them afterwards."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, group):
+        import torch.distributed as dist
+        x = x.contiguous()
+        c = x.shape[1]
+        native = x.is_cuda and backend_for(x).name == 'hip'
+        moments = torch.empty(c, 3, dtype=torch.float64, device=x.device)
+        fwd_coef = x.new_empty(c, 4)  # scale, bias, mean, invstd as the forward applied them
+        if native:
+            backend = backend_for(x)
+            y = torch.empty_like(x)
+            backend.syncbn_local_moments(x, moments)
+            dist.all_reduce(moments, op=dist.ReduceOp.SUM, group=group)
+            backend.syncbn_forward_apply(x, moments, weight, bias, running_mean, running_var,
+                                         momentum, eps, relu, y, fwd_coef)
+        else:
+            xd = x.double().reshape(x.shape[0], c, -1)
+            moments[:, 0] = xd.shape[0] * xd.shape[2]
+            moments[:, 1] = xd.sum(dim=(0, 2))
+            moments[:, 2] = (xd * xd).sum(dim=(0, 2))
+            dist.all_reduce(moments, op=dist.ReduceOp.SUM, group=group)
+            n = moments[:, 0]
+            mean = moments[:, 1] / n
+            var = (moments[:, 2] / n - mean * mean).clamp_min(0.0)
+            invstd = 1.0 / torch.sqrt(var + eps)
+            g = weight.detach().double()
+            fwd_coef[:, 0] = g * invstd
+            fwd_coef[:, 1] = bias.detach().double() - mean * g * invstd
+            fwd_coef[:, 2] = mean
+            fwd_coef[:, 3] = invstd
+            # the BIASED variance, as the reference (norm.py:68-71)
+            running_mean.copy_((1.0 - momentum) * running_mean.double() + momentum * mean)
+            running_var.copy_((1.0 - momentum) * running_var.double() + momentum * var)
+            y = x * _channel_view(fwd_coef[:, 0], x) + _channel_view(fwd_coef[:, 1], x)
+            if relu:
+                y = y.clamp_min_(0.0)
+        ctx.relu, ctx.group, ctx.native, ctx.eps = relu, group, native, eps
+        ctx.save_for_backward(x, weight, fwd_coef, moments)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        import torch.distributed as dist
+        x, weight, fwd_coef, moments = ctx.saved_tensors
+        dy = dy.contiguous()
+        c = x.shape[1]
+        sums = torch.empty(c, 2, dtype=torch.float64, device=x.device)
+        if ctx.native:
+            backend = backend_for(x)
+            dx = torch.empty_like(x)
+            dgamma, dbeta = x.new_empty(c), x.new_empty(c)
+            backend.syncbn_backward_local(dy, x, fwd_coef, moments, ctx.eps, ctx.relu, sums,
+                                          dgamma, dbeta)
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+            backend.syncbn_backward_apply(dy, x, fwd_coef, weight, sums, moments, ctx.eps,
+                                          ctx.relu, dx)
+        else:
+            # the mask in the forward's fp32 operations; xhat and the closed form in double (with few
+            # positions per channel the form cancels completely), dx rounded once
+            scale, shift = _channel_view(fwd_coef[:, 0], x), _channel_view(fwd_coef[:, 1], x)
+            g = (dy * (x * scale + shift > 0) if ctx.relu else dy).double()
+            n = moments[:, 0]
+            mean = moments[:, 1] / n
+            var = (moments[:, 2] / n - mean * mean).clamp_min(0.0)
+            invstd = 1.0 / torch.sqrt(var + ctx.eps)
+            xhat = (x.double() - _channel_view(mean, x)) * _channel_view(invstd, x)
+            axes = [0] + list(range(2, x.dim()))
+            sums[:, 0] = g.sum(dim=axes)
+            sums[:, 1] = (g * xhat).sum(dim=axes)
+            dbeta, dgamma = sums[:, 0].float(), sums[:, 1].float()
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+            a = weight.detach().double() * invstd
+            k1, k2 = sums[:, 0] / n, sums[:, 1] / n
+            dx = (_channel_view(a, x) * (g - _channel_view(k1, x) - xhat * _channel_view(k2, x))).float()
+        return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+class _NaiveSyncBN(_FusedBNReLU):
+    """Mixin over nn.BatchNorm{1,2}d: batch statistics over every rank of ``group`` while
+    training under an initialised process group (world size > 1, or
+    ``dp.force_process_group()``); otherwise -- evaluation, one rank, no group -- the fused local
+    norm.  NOT a ``FusedBNReLU{1,2}d``: every fused chain gates on those two classes, and a chain
+    would normalise with local statistics.
+
+    One deliberate difference from the reference: it averages the per-rank means with equal weight
+    per rank, which is the global batch statistic only when every rank holds the same number of
+    positions.  Here the count travels in the moments, so the result always equals BatchNorm over
+    the concatenated batch; with equal shards the two agree.  As in the reference the running
+    variance takes the biased variance and ``num_batches_tracked`` is not touched on the sync
+    path."""
+
+    def _init_sync(self, relu, group):
+        if self.momentum is None:
+            raise ValueError(f'{type(self).__name__}: momentum=None (a cumulative moving average) '
+                             'is not supported; give a float momentum')
+        self._init_fused(relu)
+        self.group = group
+
+    def forward(self, x):
+        assert x.dtype == torch.float32, f'input should be in float32 type, got {x.dtype}'
+        if not (self.training and _sync_group_active(self.group)):
+            return _FusedBNReLU.forward(self, x)
+        assert x.numel() > 0, 'SyncBN does not support empty inputs'
+        if not (self.affine and self.track_running_stats):
+            raise RuntimeError(f'{type(self).__name__}: the synchronised path needs affine=True and '
+                               'track_running_stats=True')
+        if x.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{type(self).__name__}: the synchronised path cannot be captured in '
+                               'a graph (its all-reduce is not captured); keep plain BN in a '
+                               'graphed step')
+        self._check_input_dim(x)
+        return SyncBNReLUTrain.apply(x, self.weight, self.bias, self.running_mean,
+                                     self.running_var, self.momentum, self.eps, self.fuse_relu,
+                                     self.group)
+
+
+class NaiveSyncBatchNorm1d(_NaiveSyncBN, nn.BatchNorm1d):
+    """``nn.BatchNorm1d`` (same parameters, buffers, state-dict keys) with cross-rank batch
+    statistics; norm type ``naiveSyncBN1d``.  See ``_NaiveSyncBN``."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
+                 track_running_stats=True, *, relu=False, group=None):
+        nn.BatchNorm1d.__init__(self, num_features, eps, momentum, affine, track_running_stats)
+        self._init_sync(relu, group)
+
+
+class NaiveSyncBatchNorm2d(_NaiveSyncBN, nn.BatchNorm2d):
+    """``nn.BatchNorm2d`` with cross-rank batch statistics; norm type ``naiveSyncBN2d``."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True,
+                 track_running_stats=True, *, relu=False, group=None):
+        nn.BatchNorm2d.__init__(self, num_features, eps, momentum, affine, track_running_stats)
+        self._init_sync(relu, group)

@@ -20,7 +20,7 @@ from .gather_points import gather_points
 from .group_points import (QueryAndGroup, SampleQueryGroupCat, inverted_index,
                            sample_query_group_supported)
 from .interpolate import three_interpolate, three_nn
-from .norm import FusedBNReLU1d, FusedBNReLU2d
+from .norm import FusedBNReLU1d, FusedBNReLU2d, NaiveSyncBatchNorm1d, NaiveSyncBatchNorm2d
 from .pool import group_max_pool
 
 
@@ -165,6 +165,12 @@ class ConvModule(nn.Module):
                 self.act_fused = relu_follows
             elif ntype == 'BN2d':
                 self.norm_name, norm = 'bn', FusedBNReLU2d(out_channels, relu=relu_follows)
+                self.act_fused = relu_follows
+            elif ntype in ('naiveSyncBN1d', 'naiveSyncBN2d'):
+                # batch statistics over every rank (norm.py); not a FusedBNReLU, so forward() and
+                # the fused chains leave it its own conv -> norm path
+                sync_cls = NaiveSyncBatchNorm1d if ntype == 'naiveSyncBN1d' else NaiveSyncBatchNorm2d
+                self.norm_name, norm = 'bn', sync_cls(out_channels, relu=relu_follows)
                 self.act_fused = relu_follows
             elif ntype == 'GN':
                 self.norm_name, norm = 'gn', nn.GroupNorm(norm_cfg['num_groups'],
