@@ -1,6 +1,8 @@
 """HIP kernels (through the C ABI) against the CPU oracle on identical seeded inputs.
 Index outputs must be bit-exact; fp32 outputs of deterministic kernels too; the
-atomic scatter-adds are compared at 1e-5 (sum order differs, as in the reference)."""
+atomic scatter-adds are compared at 1e-5 (sum order differs, as in the reference).
+The flat optimiser's arithmetic is held to float64 in tests/test_flat_adamw_fp64_gpu.py; its tests
+here cover the capture, the resume and the eval-coefficient cache."""
 import numpy as np
 import pytest
 import torch
