@@ -1219,6 +1219,46 @@ int nesie_sigmoid_focal_loss_backward(int n, int c, const float *x, const long l
                                       const float *grad_out, const float *grad_scalar, float scale,
                                       const float *scale_dev, float *grad_x, void *stream);
 
+/* Lovasz-Softmax loss (reference mmdet3d/models/losses/lovasz_loss.py:38-126), loss and gradient in
+ * one call.
+ *   probas: float32 class probabilities of B images, C classes and S points, element (b, c, s) at
+ *   probas[b * stride_b + c * stride_c + s * stride_s] (element strides): the channel-first
+ *   (B, C, S) tensor and the flat (P, C) one (B = 1, stride_c = 1, stride_s = C) are read in place.
+ *   labels[B, S] int64.  has_ignore / ignore: the void label.
+ * A SEGMENT is one class over all B * S points (per_image = 0) or one (image, class) pair over its
+ *   S points (per_image = 1).  In segment c, fg_i = (label_i == c) and e_i = |fg_i - p_ic| in fp32.
+ *   A label outside [0, C) that is not `ignore` is background for every class and is never an
+ *   index.  The entries are ordered by e descending, EQUAL ERRORS BY ASCENDING POINT INDEX
+ *   (torch.sort leaves ties open; the loss does not depend on them, the gradient does).  +inf and
+ *   NaN errors sort first, as torch.sort(descending=True) puts them, and reach the loss as inf or
+ *   NaN.  A void point (label == ignore) sorts after every valid point of its segment with fg = 0:
+ *   only prefixes enter the Lovasz gradient, so this equals the reference's compaction; its
+ *   gradient is 0.
+ *   With G the segment's foreground count and cf_i / cb_i the inclusive foreground / background
+ *   counts of the first i sorted entries, U_i = G + cb_i, I_i = G - cf_i:
+ *     g_i = 1 / U_i (fg_i)     g_i = I_i / (U_i (U_i - 1)) (otherwise)     g_0 = 1 when G = 0
+ *   which is jaccard_i - jaccard_{i-1} of the reference without the difference of two numbers near
+ *   1; evaluated in double from the integer counts.  loss_c = sum_i e_i g_i in double, in a fixed
+ *   order; d loss_c / d p_ic = -g_i (fg_i) or +g_i.
+ * class_mode 0: every class is averaged; 1: the classes present in the segment's labels (G > 0,
+ *   decided on the device); 2: class c counts class_mask[c] times (C ints; a class list, a negative
+ *   entry is 0).  loss[0] = mean of loss_c over the averaged classes (per_image: the mean over the
+ *   B images of each image's class mean; an image without an averaged class contributes 0 and is
+ *   still counted).  No averaged class at all: loss 0 and a zero gradient.
+ *   grad: d loss / d probas, WRITTEN in full with the strides of probas (the divisor applied).
+ * workspace: nesie_lovasz_softmax_workspace_bytes(images, classes, points) bytes, 8-byte aligned.
+ * Nothing allocates, synchronises, reads back or uses an atomic: the call captures into a graph and
+ *   gives the same bits in every run.  images, classes or points == 0 succeeds without a launch and
+ *   touches nothing.  A negative size, a class_mode outside 0 .. 2, mode 2 without a mask or a null
+ *   pointer of a non-empty problem is NESIE_ERR_INVALID_ARG; images * classes * points above
+ *   2^31 - 1025 is NESIE_ERR_UNSUPPORTED (workspace_bytes then answers 0); all before any launch. */
+size_t nesie_lovasz_softmax_workspace_bytes(int images, int classes, long long points);
+int nesie_lovasz_softmax(int images, int classes, long long points, const float *probas,
+                         long long stride_b, long long stride_c, long long stride_s,
+                         const long long *labels, int has_ignore, long long ignore, int per_image,
+                         int class_mode, const int *class_mask, float *loss, float *grad,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1884,6 +1884,39 @@ class HipKernels:
                 sample_weight, mode, float(gamma), float(alpha), grad_output, grad_scalar,
                 float(scale), scale_dev, grad_input)
 
+    @staticmethod
+    def lovasz_softmax_workspace_bytes(images, classes, points):
+        """Scratch bytes of ``lovasz_softmax`` (nesie_lovasz_softmax_workspace_bytes); 0 for an
+        empty problem and for one the kernels refuse."""
+        return _lib.load().nesie_lovasz_softmax_workspace_bytes(images, classes, points)
+
+    def lovasz_softmax(self, probas, labels, loss, grad, per_image=False, ignore=None,
+                       class_mode=1, class_mask=None, workspace=None):
+        """probas (B, C, S) float32 of ANY non-overlapping strides, labels (B, S) int64 -> loss (one
+        element) and grad (B, C, S, the strides of probas), both WRITTEN in full
+        (nesie_lovasz_softmax).  class_mode 0 all / 1 present / 2 ``class_mask`` (C int32 counts)."""
+        for t in (probas, grad):
+            if not t.is_cuda:
+                raise _no_cpu_path(t.device)
+        _check(labels, loss); _f32(probas, loss, grad)
+        if labels.dtype != torch.int64:
+            raise TypeError(f"expected int64, got {labels.dtype}")
+        assert probas.dim() == 3 and tuple(labels.shape) == (probas.shape[0], probas.shape[2])
+        assert grad.shape == probas.shape and grad.stride() == probas.stride()
+        assert loss.numel() == 1 and class_mode in (0, 1, 2)
+        b, c, s = probas.shape
+        if class_mode == 2:
+            _check(class_mask); _i32(class_mask)
+            assert class_mask.numel() == c
+        else:
+            class_mask = None
+        need = self.lovasz_softmax_workspace_bytes(b, c, s)
+        workspace = self._voxel_workspace(workspace, need, probas.device)
+        sb, sc, ss = probas.stride()
+        _launch("nesie_lovasz_softmax", probas, b, c, s, probas, sb, sc, ss, labels,
+                ignore is not None, 0 if ignore is None else int(ignore), bool(per_image),
+                int(class_mode), class_mask, loss, grad, workspace, need)
+
 
 def _row_bias_group(x, row_bias):
     if row_bias is None:

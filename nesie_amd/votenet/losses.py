@@ -1,7 +1,7 @@
 """Losses of the Nesie head.
 
 Restates ``mmdet3d/models/losses/{chamfer_distance,surface_loss,side_pred_loss,
-iou3d_loss,axis_aligned_iou_loss,gfocal_loss}.py`` and the mmdet 2.19 losses and loss plumbing they
+iou3d_loss,axis_aligned_iou_loss,gfocal_loss,lovasz_loss}.py`` and the mmdet 2.19 losses and loss plumbing they
 stand beside (``weighted_loss`` / ``weight_reduce_loss`` / MSE / L1 / SmoothL1 / CrossEntropy /
 FocalLoss; source not in the reference tree, semantics from SURVEY.md appendix C).
 """
@@ -14,6 +14,7 @@ from torch.autograd.function import once_differentiable
 from ..kernels import backend_for, injected_backend
 from ..mmdet3d_ops.axis_aligned_iou import axis_aligned_bbox_overlaps_3d
 from ..mmdet3d_ops.focal_loss import focal_backward, focal_forward
+from ..mmdet3d_ops.lovasz import lovasz_softmax_op
 from ..mmdet3d_ops.rotated_iou import cal_diou_3d, cal_giou_3d, cal_iou_3d
 
 
@@ -485,7 +486,118 @@ class _FocalLossFn(Function):
                                scale, scale_dev),) + (None,) * 7
 
 
+def lovasz_grad(gt_sorted):
+    """Gradient of the Lovasz extension w.r.t. the sorted errors (reference lovasz_loss.py:38-50,
+    Alg. 1 of the paper), float32 like the reference's.  The reference differences
+    ``1 - intersection / union`` of neighbouring entries; intersection and union are integer
+    counts, so the difference is formed here in closed form from them in float64:
+    ``1 / U`` at a foreground entry, ``I / (U (U - 1))`` at a background one."""
+    fg = gt_sorted.reshape(-1) != 0
+    cf = fg.cumsum(0)
+    at = torch.arange(1, fg.numel() + 1, device=fg.device)
+    union = (fg.sum() + (at - cf)).double()
+    inter = (fg.sum() - cf).double()
+    g = torch.where(fg, 1.0 / union, torch.where(
+        union > 1, inter / (union * (union - 1)).clamp(min=1), torch.ones_like(union)))
+    return g.float()
+
+
+def flatten_probas(probas, labels, ignore=None):
+    """(B, H, W) sigmoid output, (B, C, H, W) or (B, C, L, H, W) -> (P, C) probabilities and (P,)
+    labels, the void points removed when ``ignore`` is given (reference lovasz_loss.py:86-106).
+    Kept for code that calls it; ``lovasz_softmax`` itself neither permutes nor compacts."""
+    if probas.dim() == 3:
+        probas = probas.unsqueeze(1)
+    b, c = probas.shape[:2]
+    probas = probas.reshape(b, c, -1).permute(0, 2, 1).reshape(-1, c)
+    labels = labels.reshape(-1)
+    if ignore is None:
+        return probas, labels
+    valid = labels != ignore
+    return probas[valid], labels[valid]
+
+
+def _lovasz_segments(probas, labels, classes, per_image, ignore):
+    """probas (B, C, S) in any layout, labels (B, S) -> the loss; the checks the reference makes on
+    the way (lovasz_loss.py:71-73)."""
+    c = probas.shape[1]
+    if c == 1:
+        # the sigmoid form: one listed class k, foreground where the label is k
+        if isinstance(classes, str) or len(classes) != 1:
+            raise ValueError('Sigmoid output possible only with 1 class')
+        k = int(classes[0])
+        if k != 0:
+            # k -> 0, everything else background (-1), void (-2) first as the reference compacts first
+            fg = torch.where(labels == k, 0, -1)
+            if ignore is not None:
+                fg = torch.where(labels == ignore, -2, fg)
+                ignore = -2
+            labels, classes = fg, [0]
+    return lovasz_softmax_op(probas, labels, classes, per_image, ignore)
+
+
+def lovasz_softmax_flat(probas, labels, classes='present'):
+    """Multi-class Lovasz-Softmax loss of probas (P, C) and labels (P,); ``classes``: 'all',
+    'present' (the classes present in labels) or a list of classes to average (reference
+    lovasz_loss.py:52-82).  The (P, C) tensor is read in place, on the device by the sort-and-scan
+    kernels of csrc/lovasz.hip.  Equal errors are ordered by ascending point index."""
+    assert probas.dim() == 2 and labels.numel() == probas.shape[0]
+    return _lovasz_segments(probas.t().unsqueeze(0), labels.reshape(1, -1), classes, False, None)
+
+
+def lovasz_softmax(probas, labels, classes='present', per_image=False, ignore=None):
+    """Multi-class Lovasz-Softmax loss (reference lovasz_loss.py:109-126).  probas: (B, C, H, W)
+    class probabilities, (B, C, L, H, W) for 3-D segmentation, or (B, H, W) as the output of a
+    sigmoid; labels: (B, H, W) / (B, L, H, W) ground truth; ``per_image``: the mean of the images'
+    losses instead of the loss of the batch; ``ignore``: the void label.
+
+    Where the reference returns the Python int 0 (no class present) or an empty (0, C) tensor (no
+    valid point), this returns a 0-d zero attached to the graph with a zero gradient: neither case
+    is known without reading the device."""
+    if probas.dim() == 3:
+        probas = probas.unsqueeze(1)
+    assert probas.dim() in (4, 5), 'probas: (B, H, W), (B, C, H, W) or (B, C, L, H, W)'
+    b, c = probas.shape[:2]
+    return _lovasz_segments(probas.reshape(b, c, -1), labels.reshape(b, -1), classes, per_image,
+                            ignore)
+
+
+class Lovasz3D(nn.Module):
+    """Reference lovasz_loss.py:128-167: ``reduction`` is accepted and unused, ``weight`` only
+    decides the all-zero early return.  ``ignore_index`` (keyword only) is an extension: the
+    reference module never forwards ``ignore``."""
+
+    def __init__(self, loss_function, reduction='mean', loss_weight=1.0, per_image=False,
+                 classes='present', *, ignore_index=None):
+        super().__init__()
+        self.loss_function = loss_function
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.per_image = per_image
+        self.classes = classes
+        self.ignore_index = ignore_index
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None,
+                **kwargs):
+        if weight is not None and not torch.any(weight > 0):
+            return pred.sum() * weight.sum()  # 0
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        if self.ignore_index is None:
+            return self.loss_weight * self.loss_function(pred, target, self.classes,
+                                                         self.per_image)
+        return self.loss_weight * self.loss_function(pred, target, self.classes, self.per_image,
+                                                     self.ignore_index)
+
+
+class Lovasz3DLoss(Lovasz3D):
+    def __init__(self, reduction='mean', loss_weight=1.0, per_image=False, classes='present', *,
+                 ignore_index=None):
+        super().__init__(lovasz_softmax, reduction, loss_weight, per_image, classes,
+                         ignore_index=ignore_index)
+
+
 _LOSSES = dict(ChamferDistance=ChamferDistance, CrossEntropyLoss=CrossEntropyLoss,
+               Lovasz3DLoss=Lovasz3DLoss,
                FocalLoss=FocalLoss, GeneralDistributionFocalLoss=GeneralDistributionFocalLoss,
                IoU3DLoss=IoU3DLoss, GIoU3DLoss=GIoU3DLoss, DIoU3DLoss=DIoU3DLoss,
                AxisAlignedIoULoss=AxisAlignedIoULoss,
