@@ -17,7 +17,7 @@
 // The synchronised norm (nesie_syncbn_*: NaiveSyncBatchNorm1d/2d, reference mmdet3d/ops/norm.py:27-133)
 // is the same pipeline cut open between each local reduction and its finalise step, with float64
 // moments / sums leaving the rank for the caller's all-reduce: same pass counts.
-#include "common.h"
+#include "bn_coef.h"
 #include <stdlib.h>
 
 namespace nesie {
@@ -32,6 +32,42 @@ constexpr int BN_SPAN = 8192;  // floats of one (b, c) row handled by a stats/re
 __device__ __forceinline__ int group_shift(int group) { return group ? __ffs(group) - 1 : 62; }
 __device__ __forceinline__ size_t rb_offset(int b, int c, int c_total, long long p, int group) {
   return group ? ((size_t)b * c_total + c) * (size_t)(p / group) : (size_t)c;
+}
+
+// ---- the per-element formulas: each kernel's float4 loop (through map4) and its scalar loop for
+// rows that are not 16-byte aligned (p % 4 != 0) call the same function
+template <typename F>
+__device__ __forceinline__ float4 map4(F f, const float4 a) {
+  return make_float4(f(a.x), f(a.y), f(a.z), f(a.w));
+}
+template <typename F>
+__device__ __forceinline__ float4 map4(F f, const float4 a, const float4 b) {
+  return make_float4(f(a.x, b.x), f(a.y, b.y), f(a.z, b.z), f(a.w, b.w));
+}
+__device__ __forceinline__ float4 add4(const float4 v, float r) {
+  return make_float4(v.x + r, v.y + r, v.z + r, v.w + r);
+}
+
+// y = relu?(x * scale + bias)
+template <bool RELU>
+__device__ __forceinline__ float bn_act(float v, float sc, float bi) {
+  const float o = v * sc + bi;
+  return RELU ? fmaxf(o, 0.f) : o;
+}
+// g where the forward's ReLU let x through.  fused: the forward was the fused operand load of
+// pwconv.hip, fma(x, scale, bias); otherwise bn_act's two fp32 operations -- the same bits as the
+// forward's either way, so y need not be read
+__device__ __forceinline__ float relu_gate(float g, float v, float sc, float bi, bool fused) {
+  return (fused ? __builtin_fmaf(v, sc, bi) : v * sc + bi) > 0.f ? g : 0.f;
+}
+// dx = a (g - k1 - xhat k2), terms as bn_bwd_terms leaves them
+__device__ __forceinline__ float bn_dx(float g, float v, float a, float k1, float k2, float mean,
+                                       float invstd) {
+  return a * (g - k1 - (v - mean) * invstd * k2);
+}
+// the same in double, rounded once (the synchronised norm): ak1 = -a k1, q = a invstd k2
+__device__ __forceinline__ float syncbn_dx(float g, float v, double a, double ak1, double q, double mean) {
+  return (float)fma(mean - (double)v, q, fma(a, (double)g, ak1));
 }
 
 // partial[(c * nslice + b * sp + s) * 2 + {0,1}] = sum(x - shift), sum((x - shift)^2)
@@ -72,29 +108,21 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_stats_kernel(
   }
 }
 
-// coef[c*4 + {0,1,2,3}] = scale, bias, mean, invstd
 // Everything the statistics -> coefficients step needs (the per-slice partial sums and where
-// the results go).  The step runs inside the apply kernels: every block of a channel folds the
-// channel's partials itself (wave 0, fp64; <= a few hundred values from L2) and the first block
-// of the channel also writes the saved statistics / running statistics -- no separate
-// one-block "finalize" launch between the two streaming passes.
+// the results go: coef layout in bn_coef.h).  The step runs inside the apply kernels: every block
+// of a channel folds the channel's partials itself (wave 0, fp64; <= a few hundred values from L2)
+// and the first block of the channel also writes the saved statistics / running statistics -- no
+// separate one-block "finalize" launch between the two streaming passes.
 struct BnFwdFin {
   int nslice; double n; const float *x; long long p; const float *row_bias; int group;
-  const float *partial; const float *gamma; const float *beta; float *running_mean;
-  float *running_var; float momentum; float eps; float *save_mean; float *save_invstd;
-  float *coef;
+  const float *partial; BnTail tail;
 };
 
 // -> sh[0] = scale, sh[1] = bias (valid for every thread after the barrier inside)
 __device__ __forceinline__ void bn_fwd_finalize(const BnFwdFin &f, int c, bool writer, float *sh) {
   if (threadIdx.x < 64) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < f.nslice; i += 64) {
-      s0 += (double)f.partial[((size_t)c * f.nslice + i) * 2];
-      s1 += (double)f.partial[((size_t)c * f.nslice + i) * 2 + 1];
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
+    double s0, s1;
+    fold_pairs(f.partial, c, f.nslice, s0, s1);
     if (threadIdx.x == 0) {
       // sums are taken about the channel's first element (no shift when the producer of the
       // partials had no such element at hand: f.x == NULL)
@@ -102,26 +130,8 @@ __device__ __forceinline__ void bn_fwd_finalize(const BnFwdFin &f, int c, bool w
                                           (f.row_bias ? f.row_bias[f.group ? (size_t)c * (f.p / f.group) : (size_t)c] : 0.f))
                                : 0.0;
       const double m = s0 / f.n;
-      double var = s1 / f.n - m * m;
-      if (var < 0.0) var = 0.0;
-      const double mean = shift + m;
-      const double invstd = 1.0 / sqrt(var + (double)f.eps);
-      const double g = f.gamma ? (double)f.gamma[c] : 1.0, bt = f.beta ? (double)f.beta[c] : 0.0;
-      sh[0] = (float)(g * invstd);
-      sh[1] = (float)(bt - mean * g * invstd);
-      if (writer) {
-        if (f.running_mean) {
-          f.running_mean[c] = (float)((1.0 - f.momentum) * f.running_mean[c] + f.momentum * mean);
-          const double unbiased = f.n > 1.0 ? var * f.n / (f.n - 1.0) : var;
-          f.running_var[c] = (float)((1.0 - f.momentum) * f.running_var[c] + f.momentum * unbiased);
-        }
-        f.save_mean[c] = (float)mean;
-        f.save_invstd[c] = (float)invstd;
-        f.coef[c * 4 + 0] = sh[0];
-        f.coef[c * 4 + 1] = sh[1];
-        f.coef[c * 4 + 2] = (float)mean;
-        f.coef[c * 4 + 3] = (float)invstd;
-      }
+      const float4 q = bn_coef_finish(f.tail, c, f.n, shift + m, s1 / f.n - m * m, writer);
+      sh[0] = q.x; sh[1] = q.y;
     }
   }
   __syncthreads();
@@ -136,19 +146,14 @@ __global__ void bn_finalize_kernel(BnFwdFin f, int c_total) {
 // ---- synchronised norm: the pipeline cut open between the local reduction and the finalise ----
 // A rank's shifted fp32 partials cannot be added to another rank's (each has its own shift), so
 // they leave the rank as RAW moments in double, moments[c*3 + {0,1,2}] = n, sum(x), sum(x^2):
-// the one form a plain SUM all-reduce combines.  One wave per channel folds the partials 64 at a
-// time in double (fixed order) and un-shifts them, all in double.
+// the one form a plain SUM all-reduce combines.  One wave per channel folds the partials
+// (fold_pairs) and un-shifts them, all in double.
 __global__ __launch_bounds__(64) void syncbn_moments_kernel(
     int nslice, double n, const float *__restrict__ x, long long p,
     const float *__restrict__ partial, double *__restrict__ moments) {
   const int c = blockIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = threadIdx.x; i < nslice; i += 64) {
-    s0 += (double)partial[((size_t)c * nslice + i) * 2];
-    s1 += (double)partial[((size_t)c * nslice + i) * 2 + 1];
-  }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
+  double s0, s1;
+  fold_pairs(partial, c, nslice, s0, s1);
   if (threadIdx.x == 0) {
     const double shift = (double)x[(size_t)c * p];      // bn_stats_kernel's shift
     moments[c * 3 + 0] = n;
@@ -158,12 +163,8 @@ __global__ __launch_bounds__(64) void syncbn_moments_kernel(
 }
 
 // the statistics -> coefficients step from the all-reduced moments (n is the GLOBAL count and
-// travels in them: no host read).  running_var takes the BIASED variance, as the reference's
-// NaiveSyncBatchNorm does (mmdet3d/ops/norm.py:68-71).
-struct SyncFwdFin {
-  const double *moments; const float *gamma; const float *beta; float *running_mean;
-  float *running_var; float momentum; float eps; float *coef;
-};
+// travels in them: no host read); its tail has biased_running_var set
+struct SyncFwdFin { const double *moments; BnTail tail; };
 
 // mean, biased variance and invstd of channel c in double.  Every pass of the synchronised norm
 // derives them from the reduced moments with this one expression, so all of them see the same bits.
@@ -180,21 +181,9 @@ __device__ __forceinline__ SyncStats syncbn_stats(const double *moments, int c, 
 
 __device__ __forceinline__ void bn_fwd_finalize(const SyncFwdFin &f, int c, bool writer, float *sh) {
   if (threadIdx.x == 0) {
-    const SyncStats st = syncbn_stats(f.moments, c, f.eps);
-    const double mean = st.mean, var = st.var, invstd = st.invstd;
-    const double g = f.gamma ? (double)f.gamma[c] : 1.0, bt = f.beta ? (double)f.beta[c] : 0.0;
-    sh[0] = (float)(g * invstd);
-    sh[1] = (float)(bt - mean * g * invstd);
-    if (writer) {
-      if (f.running_mean) {
-        f.running_mean[c] = (float)((1.0 - f.momentum) * f.running_mean[c] + f.momentum * mean);
-        f.running_var[c] = (float)((1.0 - f.momentum) * f.running_var[c] + f.momentum * var);
-      }
-      f.coef[c * 4 + 0] = sh[0];
-      f.coef[c * 4 + 1] = sh[1];
-      f.coef[c * 4 + 2] = (float)mean;
-      f.coef[c * 4 + 3] = (float)invstd;
-    }
+    const SyncStats st = syncbn_stats(f.moments, c, f.tail.eps);
+    const float4 q = bn_coef_finish(f.tail, c, st.n, st.mean, st.var, writer);
+    sh[0] = q.x; sh[1] = q.y;
   }
   __syncthreads();
 }
@@ -214,21 +203,17 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_apply_kernel(
   const long long lo = (long long)blockIdx.x * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
   const int gs = group_shift(group);
+  const auto act = [=](float v) { return bn_act<RELU>(v, sc, bi); };
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
       float4 v = ld4<NT>(x + base + i);
-      if (rb) { const float r = rb[i >> gs]; v.x += r; v.y += r; v.z += r; v.w += r; }
-      float4 o = make_float4(v.x * sc + bi, v.y * sc + bi, v.z * sc + bi, v.w * sc + bi);
-      if (RELU) {
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-      }
+      if (rb) v = add4(v, rb[i >> gs]);
+      const float4 o = map4(act, v);
       st4<NT>(y + base + i, o);
     }
   } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
-      float o = (x[base + i] + (rb ? rb[i >> gs] : 0.f)) * sc + bi;
-      y[base + i] = RELU ? fmaxf(o, 0.f) : o;
-    }
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK)
+      y[base + i] = act(x[base + i] + (rb ? rb[i >> gs] : 0.f));
   }
 }
 
@@ -245,21 +230,17 @@ __global__ __launch_bounds__(BN_BLOCK) void affine_apply_kernel(
   const long long lo = (long long)blockIdx.x * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
   const int gs = group_shift(group);
+  const auto act = [=](float v) { return bn_act<RELU>(v, sc, bi); };
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
       float4 v = ld4<NT>(x + base + i);
-      if (rb) { const float r = rb[i >> gs]; v.x += r; v.y += r; v.z += r; v.w += r; }
-      float4 o = make_float4(v.x * sc + bi, v.y * sc + bi, v.z * sc + bi, v.w * sc + bi);
-      if (RELU) {
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-      }
+      if (rb) v = add4(v, rb[i >> gs]);
+      const float4 o = map4(act, v);
       st4<NT>(y + base + i, o);
     }
   } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
-      float o = (x[base + i] + (rb ? rb[i >> gs] : 0.f)) * sc + bi;
-      y[base + i] = RELU ? fmaxf(o, 0.f) : o;
-    }
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK)
+      y[base + i] = act(x[base + i] + (rb ? rb[i >> gs] : 0.f));
   }
 }
 
@@ -293,31 +274,28 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_reduce_kernel(
   const long long lo = (long long)s * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
   const int gs = group_shift(group);
+  const bool raw = raw_coef != nullptr;
+  // the gate is decided by the stored activation o where there is one; raw: o is x (fused form)
+  const auto gate = [=](float g, float o) { return raw ? relu_gate(g, o, rsc, rbi, true) : o > 0.f ? g : 0.f; };
+  const auto gxhat = [=](float g, float v) { return g * ((v - mean) * invstd); };
   float a0 = 0.f, a1 = 0.f;
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
       float4 g = *(const float4 *)(dy + base + i);      // read again by the apply pass
       float4 v = from_y ? ld4<NT>(src + base + i) : *(const float4 *)(src + base + i);
-      if (rb && !from_y) { const float r = rb[i >> gs]; v.x += r; v.y += r; v.z += r; v.w += r; }
-      if (RELU) {
-        float4 o;
-        if (raw_coef) o = make_float4(__builtin_fmaf(v.x, rsc, rbi), __builtin_fmaf(v.y, rsc, rbi),
-                                      __builtin_fmaf(v.z, rsc, rbi), __builtin_fmaf(v.w, rsc, rbi));
-        else o = from_y ? v : ld4<NT>(y + base + i);
-        g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f;
-        g.z = o.z > 0.f ? g.z : 0.f; g.w = o.w > 0.f ? g.w : 0.f;
-      }
+      if (rb && !from_y) v = add4(v, rb[i >> gs]);
+      if (RELU) g = map4(gate, g, raw || from_y ? v : ld4<NT>(y + base + i));
+      const float4 t = map4(gxhat, g, v);
       a0 += (g.x + g.y) + (g.z + g.w);
-      a1 += (g.x * ((v.x - mean) * invstd) + g.y * ((v.y - mean) * invstd)) +
-            (g.z * ((v.z - mean) * invstd) + g.w * ((v.w - mean) * invstd));
+      a1 += (t.x + t.y) + (t.z + t.w);
     }
   } else {
     for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
       float g = dy[base + i];
       float v = src[base + i];
       if (rb && !from_y) v += rb[i >> gs];
-      if (RELU) g = (raw_coef ? __builtin_fmaf(v, rsc, rbi) : from_y ? v : y[base + i]) > 0.f ? g : 0.f;
-      a0 += g; a1 += g * ((v - mean) * invstd);
+      if (RELU) g = gate(g, raw || from_y ? v : y[base + i]);
+      a0 += g; a1 += gxhat(g, v);
     }
   }
   a0 = block_sum<BN_BLOCK>(a0, sh);
@@ -328,7 +306,7 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_reduce_kernel(
   }
 }
 
-// coef[c*4 + {0,1,2}] = gamma*invstd, sum(g)/n, sum(g*xhat)/n ; dgamma, dbeta written
+// the partials of a backward reduction and what bn_bwd_terms needs to finish them
 struct BnBwdFin {
   int nslice; double n; const float *partial; const float *gamma; const float *save_invstd;
   float *dgamma; float *dbeta;
@@ -338,22 +316,12 @@ struct BnBwdFin {
 // -> sh[0] = gamma * invstd, sh[1] = sum(dy) / n, sh[2] = sum(dy * xhat) / n
 __device__ __forceinline__ void bn_bwd_finalize(const BnBwdFin &f, int c, bool writer, float *sh) {
   if (threadIdx.x < 64) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < f.nslice; i += 64) {
-      s0 += (double)f.partial[((size_t)c * f.nslice + i) * 2];
-      s1 += (double)f.partial[((size_t)c * f.nslice + i) * 2 + 1];
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
+    double s0, s1;
+    fold_pairs(f.partial, c, f.nslice, s0, s1);
     if (threadIdx.x == 0) {
-      const double g = f.gamma ? (double)f.gamma[c] : 1.0;
-      sh[0] = (float)(g * (double)f.save_invstd[(size_t)c * f.istride]);
-      sh[1] = (float)(s0 / f.n);
-      sh[2] = (float)(s1 / f.n);
-      if (writer) {
-        if (f.dbeta) f.dbeta[c] = (float)s0;
-        if (f.dgamma) f.dgamma[c] = (float)s1;
-      }
+      const BnBwdTerms t = bn_bwd_terms(s0, s1, f.n, f.gamma, f.save_invstd[(size_t)c * f.istride], c,
+                                        f.dgamma, f.dbeta, writer);
+      sh[0] = t.a; sh[1] = t.k1; sh[2] = t.k2;
     }
   }
   __syncthreads();
@@ -390,15 +358,13 @@ __global__ __launch_bounds__(BN_BLOCK) void syncbn_bwd_reduce_kernel(
   const SyncStats st = syncbn_stats(moments, c, eps);
   const long long lo = (long long)s * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
+  const auto gate = [=](float g, float v) { return relu_gate(g, v, sc, bi, false); };
   double a0 = 0.0, a1 = 0.0;   // sum(g), sum(g * (x - mean)); invstd is applied once at the end
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
       float4 g = *(const float4 *)(dy + base + i);      // both read again by the apply pass
       const float4 v = *(const float4 *)(x + base + i);
-      if (RELU) {
-        g.x = v.x * sc + bi > 0.f ? g.x : 0.f; g.y = v.y * sc + bi > 0.f ? g.y : 0.f;
-        g.z = v.z * sc + bi > 0.f ? g.z : 0.f; g.w = v.w * sc + bi > 0.f ? g.w : 0.f;
-      }
+      if (RELU) g = map4(gate, g, v);
       a0 += ((double)g.x + (double)g.y) + ((double)g.z + (double)g.w);
       a1 = fma((double)g.x, (double)v.x - st.mean, a1);
       a1 = fma((double)g.y, (double)v.y - st.mean, a1);
@@ -409,7 +375,7 @@ __global__ __launch_bounds__(BN_BLOCK) void syncbn_bwd_reduce_kernel(
     for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
       float g = dy[base + i];
       const float v = x[base + i];
-      if (RELU) g = v * sc + bi > 0.f ? g : 0.f;
+      if (RELU) g = gate(g, v);
       a0 += (double)g;
       a1 = fma((double)g, (double)v - st.mean, a1);
     }
@@ -429,13 +395,8 @@ __global__ __launch_bounds__(64) void syncbn_bwd_fold_kernel(
     int nslice, const double *__restrict__ partial, double *__restrict__ sums,
     float *__restrict__ dgamma, float *__restrict__ dbeta) {
   const int c = blockIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = threadIdx.x; i < nslice; i += 64) {
-    s0 += partial[((size_t)c * nslice + i) * 2];
-    s1 += partial[((size_t)c * nslice + i) * 2 + 1];
-  }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
+  double s0, s1;
+  fold_pairs(partial, c, nslice, s0, s1);
   if (threadIdx.x == 0) {
     sums[c * 2 + 0] = s0; sums[c * 2 + 1] = s1;
     if (dbeta) dbeta[c] = (float)s0;
@@ -461,28 +422,16 @@ __global__ __launch_bounds__(BN_BLOCK) void syncbn_bwd_apply_kernel(
   const size_t base = ((size_t)b * c_total + c) * p;
   const long long lo = (long long)blockIdx.x * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
+  const auto dxf = [=](float g, float v) {
+    return syncbn_dx(RELU ? relu_gate(g, v, sc, bi, false) : g, v, a, ak1, q, mean);
+  };
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
-      float4 g = ld4<NT>(dy + base + i);
-      const float4 v = ld4<NT>(x + base + i);
-      if (RELU) {
-        g.x = v.x * sc + bi > 0.f ? g.x : 0.f; g.y = v.y * sc + bi > 0.f ? g.y : 0.f;
-        g.z = v.z * sc + bi > 0.f ? g.z : 0.f; g.w = v.w * sc + bi > 0.f ? g.w : 0.f;
-      }
-      float4 r;
-      r.x = (float)fma(mean - (double)v.x, q, fma(a, (double)g.x, ak1));
-      r.y = (float)fma(mean - (double)v.y, q, fma(a, (double)g.y, ak1));
-      r.z = (float)fma(mean - (double)v.z, q, fma(a, (double)g.z, ak1));
-      r.w = (float)fma(mean - (double)v.w, q, fma(a, (double)g.w, ak1));
+      const float4 r = map4(dxf, ld4<NT>(dy + base + i), ld4<NT>(x + base + i));
       st4<NT>(dx + base + i, r);
     }
   } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
-      float g = dy[base + i];
-      const float v = x[base + i];
-      if (RELU) g = v * sc + bi > 0.f ? g : 0.f;
-      dx[base + i] = (float)fma(mean - (double)v, q, fma(a, (double)g, ak1));
-    }
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) dx[base + i] = dxf(dy[base + i], x[base + i]);
   }
 }
 
@@ -506,25 +455,15 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply_kernel(
   const long long lo = (long long)blockIdx.x * BN_SPAN;
   const long long hi = lo + BN_SPAN < p ? lo + BN_SPAN : p;
   const int gs = group_shift(group);
+  const bool fused = fused_mask != 0;
+  const auto dxf = [=](float g, float v) {
+    return bn_dx(RELU ? relu_gate(g, v, sc, bi, fused) : g, v, a, k1, k2, mean, invstd);
+  };
   if ((p & 3) == 0) {
     for (long long i = lo + threadIdx.x * 4; i < hi; i += BN_BLOCK * 4) {
-      float4 g = ld4<NT>(dy + base + i);
       float4 v = ld4<NT>(x + base + i);
-      if (row_bias) { const float r = row_bias[rbase + (i >> gs)]; v.x += r; v.y += r; v.z += r; v.w += r; }
-      if (RELU) {
-        if (fused_mask) {   // the forward applied fma(x, scale, bias) (pwconv.hip operand load)
-          g.x = __builtin_fmaf(v.x, sc, bi) > 0.f ? g.x : 0.f; g.y = __builtin_fmaf(v.y, sc, bi) > 0.f ? g.y : 0.f;
-          g.z = __builtin_fmaf(v.z, sc, bi) > 0.f ? g.z : 0.f; g.w = __builtin_fmaf(v.w, sc, bi) > 0.f ? g.w : 0.f;
-        } else {
-          g.x = v.x * sc + bi > 0.f ? g.x : 0.f; g.y = v.y * sc + bi > 0.f ? g.y : 0.f;
-          g.z = v.z * sc + bi > 0.f ? g.z : 0.f; g.w = v.w * sc + bi > 0.f ? g.w : 0.f;
-        }
-      }
-      float4 r;
-      r.x = a * (g.x - k1 - (v.x - mean) * invstd * k2);
-      r.y = a * (g.y - k1 - (v.y - mean) * invstd * k2);
-      r.z = a * (g.z - k1 - (v.z - mean) * invstd * k2);
-      r.w = a * (g.w - k1 - (v.w - mean) * invstd * k2);
+      if (row_bias) v = add4(v, row_bias[rbase + (i >> gs)]);
+      const float4 r = map4(dxf, ld4<NT>(dy + base + i), v);
       st4<NT>(dx + base + i, r);
       if (d_row_bias) {
         // gradient of the broadcast term = sum of dx over its `group` positions = the
@@ -535,13 +474,9 @@ __global__ __launch_bounds__(BN_BLOCK) void bn_bwd_apply_kernel(
       }
     }
   } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK) {
-      float g = dy[base + i];
-      // (the grouped row-bias form requires p % 4 == 0, checked on the host; the per-channel one not)
-      const float v = x[base + i] + (row_bias ? row_bias[rbase + (i >> gs)] : 0.f);
-      if (RELU) g = (fused_mask ? __builtin_fmaf(v, sc, bi) : v * sc + bi) > 0.f ? g : 0.f;
-      dx[base + i] = a * (g - k1 - (v - mean) * invstd * k2);
-    }
+    // (the grouped row-bias form requires p % 4 == 0, checked on the host; the per-channel one not)
+    for (long long i = lo + threadIdx.x; i < hi; i += BN_BLOCK)
+      dx[base + i] = dxf(dy[base + i], x[base + i] + (row_bias ? row_bias[rbase + (i >> gs)] : 0.f));
   }
 }
 
@@ -688,7 +623,7 @@ extern "C" int nesie_bn_relu_forward(int b, int c, long long p, const float *x,
   }
   hipStream_t s = (hipStream_t)stream;
   const int sp = bn_sp(p), nslice = b * sp;
-  float *partial = (float *)workspace, *coef = fwd_coef;  // [C][4]: scale, bias, mean, invstd
+  float *partial = (float *)workspace;
   dim3 grid(sp, c, b);
   NESIE_REQUIRE(!pre_partial || (pre_nslice >= 1 && !row_bias), W);
   if (!pre_partial)
@@ -697,8 +632,9 @@ extern "C" int nesie_bn_relu_forward(int b, int c, long long p, const float *x,
   // the producer's partials are unshifted sums: no shift element (x = NULL in the finalize)
   const BnFwdFin fin{pre_partial ? pre_nslice : nslice, (double)b * (double)p,
                      pre_partial ? nullptr : x, p, row_bias, group,
-                     pre_partial ? pre_partial : partial, gamma, beta,
-                     running_mean, running_var, momentum, eps, save_mean, save_invstd, coef};
+                     pre_partial ? pre_partial : partial,
+                     BnTail{gamma, beta, running_mean, running_var, momentum, eps, fwd_coef, save_mean,
+                            save_invstd}};
   const bool nt = bn_use_nt((long long)b * c * p);
   with_bool(relu, [&](auto R) {
     with_bool(nt, [&](auto N) {
@@ -733,11 +669,10 @@ extern "C" int nesie_bn_relu_backward(int b, int c, long long p, const float *dy
   NESIE_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)y) & 15) == 0, W);
   hipStream_t s = (hipStream_t)stream;
   const int sp = bn_sp(p), nslice = b * sp;
-  float *partial = (float *)workspace, *coef = partial + (size_t)c * nslice * 2;
+  float *partial = (float *)workspace;
   dim3 grid(sp, c, b);
   const bool nt = bn_use_nt((long long)b * c * p);
   const BnBwdFin fin{nslice, (double)b * (double)p, partial, gamma, save_invstd ? save_invstd : fwd_coef + 3, dgamma, dbeta, save_invstd ? 1 : 4};
-  (void)coef;
   with_bool(relu, [&](auto R) {
     with_bool(nt, [&](auto N) {
       hipLaunchKernelGGL((bn_bwd_reduce_kernel<R(), N()>), grid, dim3(BN_BLOCK), 0, s, c, p, sp, dy, x, y,
@@ -827,7 +762,8 @@ extern "C" int nesie_syncbn_forward_apply(int b, int c, long long p, const float
   if (st) return st;
   NESIE_REQUIRE(x && y && moments && fwd_coef && syncbn_aligned(p, x, y, nullptr), W);
   NESIE_REQUIRE((running_mean == nullptr) == (running_var == nullptr), W);
-  const SyncFwdFin fin{moments, gamma, beta, running_mean, running_var, momentum, eps, fwd_coef};
+  SyncFwdFin fin{moments, BnTail{gamma, beta, running_mean, running_var, momentum, eps, fwd_coef}};
+  fin.tail.biased_running_var = true;
   const bool nt = bn_use_nt((long long)b * c * p);
   with_bool(relu, [&](auto R) {
     with_bool(nt, [&](auto N) {
@@ -922,8 +858,9 @@ extern "C" int nesie_bn_relu_maxpool_forward(int b, int c, int m, int ns, const 
   float *partial = (float *)workspace;
   hipLaunchKernelGGL(bn_stats_kernel, dim3(sp, c, b), dim3(BN_BLOCK), 0, s, c, p, sp, x,
                      (const float *)nullptr, 1, partial, 0);
-  const BnFwdFin fin{nslice, (double)b * (double)p, x, p, nullptr, 1, partial, gamma, beta,
-                     running_mean, running_var, momentum, eps, save_mean, save_invstd, fwd_coef};
+  const BnFwdFin fin{nslice, (double)b * (double)p, x, p, nullptr, 1, partial,
+                     BnTail{gamma, beta, running_mean, running_var, momentum, eps, fwd_coef, save_mean,
+                            save_invstd}};
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(64), 0, s, fin, c);
   const long long rows = (long long)b * c * m;
   const int lpr = ns / 4;

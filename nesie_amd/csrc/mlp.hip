@@ -2,7 +2,7 @@
 // MLPs on the fp32 matrix cores of gfx950 (mmcv ConvModule(Conv2d 1x1, BN2d, ReLU):
 // mmdet3d/ops/pointnet_modules/point_sa_module.py:277-289; dense_heads/
 // side_pooling_module.py:346-358).  The layer kernel proper is pwconv.hip.
-#include "common.h"
+#include "bn_coef.h"
 #include <stdlib.h>
 
 namespace nesie {
@@ -43,19 +43,8 @@ __global__ void mlp_stat_finalize_kernel(int c_total, int nparts, double n,
   }
   if (threadIdx.x != 0) return;
   const double mean = sh[0][0] / n;
-  double var = sh[1][0] / n - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)eps);
-  if (running_mean) {
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-  }
-  const double g = gamma ? (double)gamma[c] : 1.0, bt = beta ? (double)beta[c] : 0.0;
-  coef[c * 4 + 0] = (float)(g * invstd);
-  coef[c * 4 + 1] = (float)(bt - mean * g * invstd);
-  coef[c * 4 + 2] = (float)mean;
-  coef[c * 4 + 3] = (float)invstd;
+  const BnTail tail{gamma, beta, running_mean, running_var, momentum, eps, coef};
+  bn_coef_finish(tail, c, n, mean, sh[1][0] / n - mean * mean);
 }
 }  // namespace nesie
 
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(
     const float *__restrict__ bnz, const float *__restrict__ bnb) {
   // bnb != NULL: `dy` is the gradient dA of relu(bn(Z)), Z = `bnz` (same layout); the norm backward's
   // apply pass runs on the load, dZ = a g + (e0 - (z - mean) d1), g = dA [fma(z, scale, shift) > 0],
-  // bnb[row] = (scale, shift, a, mean, d1, e0, -, -) (pw_bnb_coef_kernel) -- dZ is never written
+  // bnb[row]: pw_bnb_coef_kernel's record (layout in bn_coef.h) -- dZ is never written
   // (nobody else reads it when the layer's input needs no gradient: the first layer of SA1).
   constexpr int MT = WM * MB * 32, NT = WN * NB * 32;  // padded Cout, Cin covered
   extern __shared__ float lds[];                      // [MT + NT][WG_P]
@@ -658,18 +647,8 @@ __global__ __launch_bounds__(256) void k4_stat_finalize_kernel(double n, const d
     mean += wj * mu[j];
     for (int k = 0; k < 4; ++k) var += wj * (double)w0[c * 4 + k] * cov[j][k];
   }
-  if (var < 0.0) var = 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)eps);
-  if (running_mean) {
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-  }
-  const double g = gamma ? (double)gamma[c] : 1.0, bt = beta ? (double)beta[c] : 0.0;
-  coef[c * 4 + 0] = (float)(g * invstd);
-  coef[c * 4 + 1] = (float)(bt - mean * g * invstd);
-  coef[c * 4 + 2] = (float)mean;
-  coef[c * 4 + 3] = (float)invstd;
+  const BnTail tail{gamma, beta, running_mean, running_var, momentum, eps, coef};
+  bn_coef_finish(tail, c, n, mean, var);
 }
 
 static int stream_cols(int b, long long p) {

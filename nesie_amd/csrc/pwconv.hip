@@ -5,6 +5,7 @@
 // library in about a minute instead of five.
 #include <algorithm>
 #include "pwconv_fwd.h"
+#include "bn_coef.h"
 #include <stdlib.h>
 
 namespace nesie {
@@ -70,22 +71,9 @@ __global__ __launch_bounds__(64) void pw_stats_finalize_kernel(
     n = nn;
   }
   if (threadIdx.x != 0) return;
-  const double var = n > 0.0 ? m2 / n : 0.0;
-  const double invstd = 1.0 / sqrt(var + (double)eps);
-  if (running_mean) {
-    // chan_bias: the bias of the convolution in front of the norm.  The layer kernel never adds
-    // it (the mean subtraction removes it from every normalised value); the running mean of the
-    // biased output differs from the unbiased one by exactly the bias
-    const double shown = mean + (chan_bias ? (double)chan_bias[ch] : 0.0);
-    running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * shown);
-    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
-    running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unbiased);
-  }
-  const double gm = gamma ? (double)gamma[ch] : 1.0, bt = beta ? (double)beta[ch] : 0.0;
-  coef[ch * 4 + 0] = (float)(gm * invstd);
-  coef[ch * 4 + 1] = (float)(bt - mean * gm * invstd);
-  coef[ch * 4 + 2] = (float)mean;
-  coef[ch * 4 + 3] = (float)invstd;
+  BnTail tail{gamma, beta, running_mean, running_var, momentum, eps, coef};
+  tail.chan_bias = chan_bias;
+  bn_coef_finish(tail, ch, n, mean, n > 0.0 ? m2 / n : 0.0);
 }
 
 // The pooling tail after the layer kernel: combine the G / PG partial extrema of every group,

@@ -1,6 +1,7 @@
 // Weight-gradient kernels of the pointwise-convolution layers (see pwconv_fwd.h for the layer
 // kernel and pwconv.hip for the host side of the forward family).
 #include "pwconv_fwd.h"
+#include "bn_coef.h"
 
 using namespace nesie;
 
@@ -663,10 +664,9 @@ extern "C" size_t nesie_pw_wgrad_workspace_bytes(int nb, int ng, int co, int ci,
 }
 
 namespace nesie {
-// bnb[c] = (scale, shift, a, mean, d1, e0, -, -) of channel c = g * co + r from the reduction
-// partials the input-gradient launch left (partial[(c * nslots + i) * 2 + {0, 1}] = sum g, sum g zhat),
-// the layer's folded forward coefficients z_coef[c] = (scale, shift, mean, invstd) and gamma;
-// dgamma / dbeta written on the way (fp64 sums, as bn_bwd_finalize in bn.hip)
+// bnb[c] (layout in bn_coef.h) of channel c = g * co + r from the reduction partials the
+// input-gradient launch left (partial[(c * nslots + i) * 2 + {0, 1}] = sum g, sum g zhat), the
+// layer's folded forward coefficients z_coef[c] and gamma; dgamma / dbeta written on the way
 __global__ __launch_bounds__(64) void pw_bnb_coef_kernel(int channels, int nslots, double count,
                                                          const float *__restrict__ part,
                                                          const float *__restrict__ z_coef,
@@ -674,35 +674,14 @@ __global__ __launch_bounds__(64) void pw_bnb_coef_kernel(int channels, int nslot
                                                          float *__restrict__ bnb, float *__restrict__ dgamma,
                                                          float *__restrict__ dbeta) {
   const int c = blockIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  const float2 *pc = (const float2 *)part + (size_t)c * nslots;
-  int i = threadIdx.x;
-  for (; i + 192 < nslots; i += 256) {           // four loads in flight, added in slot order
-    float2 q[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) q[u] = pc[i + 64 * u];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { s0 += (double)q[u].x; s1 += (double)q[u].y; }
-  }
-  for (; i < nslots; i += 64) {
-    const float2 q = pc[i];
-    s0 += (double)q.x;
-    s1 += (double)q.y;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s0 += __shfl_xor(s0, off, 64);
-    s1 += __shfl_xor(s1, off, 64);
-  }
+  double s0, s1;
+  fold_pairs(part, c, nslots, s0, s1);
   if (threadIdx.x == 0) {
     const float invstd = z_coef[c * 4 + 3];
-    const float a = (float)((gamma ? (double)gamma[c] : 1.0) * (double)invstd);
-    const float k1 = (float)(s0 / count), k2 = (float)(s1 / count);
+    const BnBwdTerms t = bn_bwd_terms(s0, s1, count, gamma, invstd, c, dgamma, dbeta);
     float *o = bnb + (size_t)c * 8;
-    o[0] = z_coef[c * 4 + 0]; o[1] = z_coef[c * 4 + 1]; o[2] = a; o[3] = z_coef[c * 4 + 2];
-    o[4] = a * invstd * k2; o[5] = -a * k1; o[6] = 0.f; o[7] = 0.f;
-    if (dbeta) dbeta[c] = (float)s0;
-    if (dgamma) dgamma[c] = (float)s1;
+    o[0] = z_coef[c * 4 + 0]; o[1] = z_coef[c * 4 + 1]; o[2] = t.a; o[3] = z_coef[c * 4 + 2];
+    o[4] = t.a * invstd * t.k2; o[5] = -t.a * t.k1; o[6] = 0.f; o[7] = 0.f;
   }
 }
 

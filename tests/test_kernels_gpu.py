@@ -516,7 +516,12 @@ def test_group_max_pool_matches_aten(oracle_kernels, hip_device, shape):
 
 @pytest.mark.parametrize("shape,relu", [((8, 64, 2048, 16), True), ((2, 128, 1024), True),
                                         ((3, 5, 7), False), ((2, 259, 33), True),
-                                        ((4, 256, 512, 4), False), ((1, 1, 1000), True)])
+                                        ((4, 256, 512, 4), False), ((1, 1, 1000), True),
+                                        # more partials per channel than the fold's 64 lanes: nslice = 193,
+                                        # 257, 449 reach its four-wide branch (lane + 192 < nslice), 64 fills
+                                        # the lanes exactly; (.., 4) is the float4 path, (.., 5) the scalar one
+                                        ((193, 2, 4), True), ((257, 2, 4), True), ((449, 1, 5), True),
+                                        ((64, 3, 5), False)])
 def test_fused_bn_relu_matches_aten(hip_device, shape, relu):
     """nesie_bn_relu_forward/backward vs torch batch_norm(+relu) evaluated on the CPU."""
     from nesie_amd.mmdet3d_ops.norm import FusedBNReLU1d, FusedBNReLU2d
